@@ -153,8 +153,35 @@ def _reduce(torch, dist, value, op, dev, rehearse):
     return float(t.item())
 
 
+DUMP_BUDGET = 60 << 20  # bytes of --dump-outputs arrays (under 64 MB with the .npy headers)
+
+
+def dump_outputs(torch, out_dir, k, d_idx, d_cnt, d_nrm):
+    """--dump-outputs: what the timed step hands its caller after the last timed step -- the k entries of each neighbour row
+    (knn_idx, float64: exact for any index), the neighbour counts (knn_cnt, float64) and, when the step computes them, the normals
+    (normals, float32).  Every row when they fit in DUMP_BUDGET, otherwise a fixed, seeded sample of rows in ascending order;
+    rows.npy (float64) names the rows written.  With N > 1 these are rank 0's buffers: rows outside its shard stay 0."""
+    n = d_cnt.shape[0]
+    per_row = 8 * k + 8 + 8 + (12 if d_nrm is not None else 0)
+    keep = min(n, DUMP_BUDGET // per_row)
+    if keep == n:
+        rows = np.arange(n, dtype=np.int64)
+    else:
+        rows = np.sort(np.random.default_rng(20240).choice(n, keep, replace=False)).astype(np.int64)
+    sel = torch.from_numpy(rows).to(d_idx.device)
+    arrays = {"rows": rows.astype(np.float64),
+              "knn_idx": d_idx.index_select(0, sel)[:, :k].cpu().numpy().astype(np.float64),
+              "knn_cnt": d_cnt.index_select(0, sel).cpu().numpy().astype(np.float64)}
+    if d_nrm is not None:
+        arrays["normals"] = d_nrm.index_select(0, sel).cpu().numpy().astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    for key, a in arrays.items():
+        np.save(os.path.join(out_dir, key + ".npy"), a)
+    return {"dir": out_dir, "rows": int(keep), "of_rows": int(n), "arrays": sorted(arrays)}
+
+
 def run_workload(pkg, torch, dist, name, rank, world, steps, warmup, want_profile, rehearse=False, side=True, collective=False,
-                 at_curve_positions=False):
+                 at_curve_positions=False, dump_dir=None):
     kind, n, seed, k = WORKLOADS[name]
     dev = torch.device("cuda", torch.cuda.current_device())
     pts = make_cloud(pkg, kind, n, seed)
@@ -240,6 +267,9 @@ def run_workload(pkg, torch, dist, name, rank, world, steps, warmup, want_profil
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     prof = ix.profile_end() if want_profile else None
+    dumped = None
+    if dump_dir and rank == 0:  # before the side measurements below write into the same buffers
+        dumped = dump_outputs(torch, dump_dir, k, d_idx, d_cnt, None if streaming else d_nrm)
     complete = int((d_cnt == k).sum().item())  # rows this rank filled with k neighbours
     if world > 1:
         elapsed = _reduce(torch, dist, elapsed, dist.ReduceOp.MAX, dev, rehearse)
@@ -307,7 +337,7 @@ def run_workload(pkg, torch, dist, name, rank, world, steps, warmup, want_profil
            "mqps": n * steps / elapsed / 1e6, "first_build_ms": first_build_ms, "rebuild_ms": rebuild_ms,
            "profile": prof, "shard": (first, count), "pts": pts, "complete": complete,
            "min_count": int(d_cnt.min().item()) if world == 1 else None, "grid": grid,
-           "local_index": ix.shard_info() if local else None, "first_step_ms": first_step_ms, "row_pitch": pitch,
+           "local_index": ix.shard_info() if local else None, "dumped": dumped, "first_step_ms": first_step_ms, "row_pitch": pitch,
            "cut": ("work: one group in 16 sampled on a whole-cloud index, %.1f ms of set-up per rank" % cut_ms) if by_work else "equal query counts"}
     ix.close()
     return res
@@ -537,6 +567,9 @@ def main():
     ap.add_argument("--no-configs", action="store_true",
                     help="skip extra.configs (BASELINE.json's other configurations, the latency shapes and the end-to-end figure, each "
                          "in a child process: about two minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (neighbour rows and counts, normals; a fixed, "
+                         "seeded sample of rows when the whole would pass 60 MB) as DIR/<name>.npy; rank 0's buffers when N > 1")
     ap.add_argument("--with-range-consumers", action="store_true",
                     help="also run tools/filter_bench.py (bilateral filter, WLOP: extras outside the hot path) and report it under extra")
     ap.add_argument("--with-1m", action="store_true",
@@ -544,6 +577,8 @@ def main():
                          "default command launches k_knn on the headline workload only (its rocprofv3 average then "
                          "equals roofline.avg_launch_ms)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     pkg = importlib.import_module("point-cloud-processing_amd")
     if args.config_child:
@@ -597,7 +632,8 @@ def main():
 
     side = not args.no_extra
     main_res = run_workload(pkg, torch, dist, args.workload, rank, world, args.steps, args.warmup, want_profile=True,
-                            rehearse=rehearse, side=side, collective=collective, at_curve_positions=args.rows_at_curve_positions)
+                            rehearse=rehearse, side=side, collective=collective, at_curve_positions=args.rows_at_curve_positions,
+                            dump_dir=args.dump_outputs)
     n, k = main_res["n"], main_res["k"]
 
     extra = {"index_build_ms_first": round(main_res["first_build_ms"], 3), "shard_of_rank0": list(main_res["shard"]),
@@ -618,6 +654,8 @@ def main():
     if main_res["local_index"]:
         extra["rank_local_index_of_rank0"] = main_res["local_index"]
     extra["rows_with_k_neighbours_all_ranks"] = main_res["complete"]  # = points when the shards cover the cloud exactly once
+    if main_res["dumped"]:
+        extra["dumped_outputs"] = main_res["dumped"]
     if rehearse:
         extra["rehearsal"] = "one GPU, gloo: functional check of the N > 1 path, not a measurement"
     if collective:

@@ -15,8 +15,9 @@
    spaced query points each -- (d2,index)-sorted 15-NN rows, PCA normals with their eigenvalues, sphere-range counts at
    2 % of the bounding-box diagonal -- from brute force, after the restated octree and kd-tree were checked to agree.
 
-Run from the repo root in the build container: python tests/golden/make_golden.py
-(steps 2 and 4 copy from /root/reference when it is there; the other steps do not need it).
+Run from the repo root: python tests/golden/make_golden.py [REFERENCE_CHECKOUT]
+(steps 2 and 4 copy the data files from REFERENCE_CHECKOUT/examples/data when it is given; otherwise they reuse the committed
+copies, and the other steps do not need it).
 """
 import json
 import os
@@ -122,10 +123,15 @@ EXTRA_ROWS = 256
 EXTRA_RADIUS_FRACTION = 0.02  # of the bounding-box diagonal
 
 
+def reference_data(name):
+    """REFERENCE_CHECKOUT/examples/data/<name>.ply, or None when no reference checkout was given."""
+    return os.path.join(sys.argv[1], "examples", "data", name + ".ply") if len(sys.argv) > 1 else None
+
+
 def extra_cloud(pkg, O, name):
-    src = "/root/reference/examples/data/%s.ply" % name
+    src = reference_data(name)
     dst = os.path.join(HERE, name + ".ply")
-    if os.path.exists(src):
+    if src:
         shutil.copyfile(src, dst)
     pts, _ = pkg.ply.read_ply(dst)
     qsel = np.linspace(0, len(pts) - 1, EXTRA_ROWS).astype(np.int64)
@@ -152,9 +158,9 @@ def extra_cloud(pkg, O, name):
 def main():
     with open(os.path.join(HERE, "reference_kats.json"), "w") as f:
         json.dump(kats(), f, indent=1)
-    src = "/root/reference/examples/data/stanford_bunny.ply"
+    src = reference_data("stanford_bunny")
     dst = os.path.join(HERE, "stanford_bunny.ply")
-    if os.path.exists(src):
+    if src:
         shutil.copyfile(src, dst)
 
     import importlib
