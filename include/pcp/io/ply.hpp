@@ -21,6 +21,7 @@
 #ifndef PCP_IO_PLY_HPP
 #define PCP_IO_PLY_HPP
 
+#include "pcp/common/mesh_triangle.hpp"
 #include "pcp/common/normals/normal.hpp"
 #include "pcp/common/points/point.hpp"
 
@@ -278,6 +279,58 @@ inline void write_ply(std::filesystem::path const& path, std::vector<Point> cons
     std::ofstream ofs{path.string(), std::ios::binary};
     if (!ofs.is_open()) return;
     write_ply<Point, Normal>(ofs, vertices, normals, format);
+}
+
+// The shared-vertex mesh overloads (reference ply.hpp:478-600): `element vertex` (x, y, z) then `element face`
+// (property list uchar uint vertex_indices).  Chosen over the point + normal overloads by partial ordering: the second
+// vector holds shared_vertex_mesh_triangle.
+template <class Point, class Index, std::enable_if_t<std::is_integral_v<Index>, int> = 0>
+inline void write_ply(std::ostream& os, std::vector<Point> const& vertices, std::vector<common::shared_vertex_mesh_triangle<Index>> const& triangles,
+                      ply_format_t format = ply_format_t::ascii)
+{
+    char const* const vt = std::is_same_v<typename Point::coordinate_type, double> ? "double" : "float";
+    char const* const fmt = format == ply_format_t::ascii                  ? "ascii"
+                            : format == ply_format_t::binary_little_endian ? "binary_little_endian"
+                                                                           : "binary_big_endian";
+    os << "ply\nformat " << fmt << " 1.0\n"
+       << "element vertex " << vertices.size() << "\nproperty " << vt << " x\nproperty " << vt << " y\nproperty " << vt << " z\n"
+       << "element face " << triangles.size() << "\nproperty list uchar uint vertex_indices\nend_header\n";
+    if (format == ply_format_t::ascii)
+    {
+        for (auto const& p : vertices) os << std::to_string(p.x()) << " " << std::to_string(p.y()) << " " << std::to_string(p.z()) << "\n";
+        for (auto const& t : triangles)
+            os << "3 " << std::to_string(t.indices()[0]) << " " << std::to_string(t.indices()[1]) << " " << std::to_string(t.indices()[2]) << "\n";
+        return;
+    }
+    bool const swap = (format == ply_format_t::binary_little_endian) != is_machine_little_endian();
+    std::string bytes;
+    bytes.reserve(vertices.size() * 12u + triangles.size() * 13u);
+    for (auto const& p : vertices)
+        detail::append_floats(bytes, static_cast<float>(p.x()), static_cast<float>(p.y()), static_cast<float>(p.z()), swap);
+    for (auto const& t : triangles)
+    {
+        bytes.push_back(static_cast<char>(3));
+        for (int c = 0; c < 3; ++c)
+        {
+            std::uint32_t v = static_cast<std::uint32_t>(t.indices()[c]);
+            if (swap) v = (v >> 24) | ((v >> 8) & 0xFF00u) | ((v << 8) & 0xFF0000u) | (v << 24);
+            char b[4];
+            std::memcpy(b, &v, 4);
+            bytes.append(b, 4);
+        }
+    }
+    os.write(bytes.data(), static_cast<std::streamsize>(bytes.size()));
+}
+
+template <class Point, class Index, std::enable_if_t<std::is_integral_v<Index>, int> = 0>
+inline void write_ply(std::filesystem::path const& path, std::vector<Point> const& vertices,
+                      std::vector<common::shared_vertex_mesh_triangle<Index>> const& triangles, ply_format_t format = ply_format_t::ascii)
+{
+    if (!path.has_extension() || path.extension() != ".ply") return;
+    if (vertices.empty() || triangles.empty()) return;  // (reference ply.hpp:487-491)
+    std::ofstream ofs{path.string(), std::ios::binary};
+    if (!ofs.is_open()) return;
+    write_ply(static_cast<std::ostream&>(ofs), vertices, triangles, format);
 }
 
 } // namespace io

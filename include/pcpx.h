@@ -449,6 +449,55 @@ int pcpx_kd_knn_batch(pcpx_kd_index* idx, const float* queries, uint64_t nq, uin
 int pcpx_kd_range_aabb_batch(pcpx_kd_index* idx, const float* boxes, uint64_t nb, uint64_t* out_offsets, uint32_t* out_idx,
                              uint64_t idx_capacity);
 
+/* ---- surface reconstruction: replaces pcp::algorithm::isosurface::surface_nets and the SDF of ---------------------------
+ * examples/tangent_plane_surface_reconstruction.cpp:233-455 --------------------------------------------------------------- */
+/* pcp::common::regular_grid3d_t<float> (include/pcp/common/regular_grid3d.hpp): origin, voxel size, voxels per axis.  A grid
+ * has (sx+1)(sy+1)(sz+1) corners; corner (i,j,k) is at (x + i*dx, y + j*dy, z + k*dz) and is entry i + j*(sx+1) +
+ * k*(sx+1)*(sy+1) of a field. */
+typedef struct pcpx_grid3d {
+    float x, y, z, dx, dy, dz;
+    uint64_t sx, sy, sz;
+} pcpx_grid3d;
+/* regular_grid_containing (regular_grid3d.hpp:63-90), including its quirk: the origin moves back by dx on all three axes. */
+int pcpx_regular_grid_containing(const float min3[3], const float max3[3], const uint64_t dims[3], pcpx_grid3d* out);
+/* Naive surface nets over a scalar field given at the grid's corners (surface_nets.hpp:357-650, the overload that marches
+ * over the whole grid): a corner is positive iff s >= isovalue, a cube with a bipolar edge gets one vertex (the centroid of
+ * its edge crossings, mapped to the world as the reference does, bit for bit), and every active cube with i, j, k >= 1
+ * emits two triangles per quad whose three neighbour cubes are active.  Deterministic order: vertices by ascending cube
+ * index i + j*sx + k*sx*sy, triangles by (cube, quad 0..2, triangle 0..1).  Every cube is meshed once (the reference's loop
+ * revisits or leaves the grid when sx or sy is strictly the longest dimension).  d_out_xyz: V x 3 floats,
+ * d_out_tri: T x 3 uint32 vertex indices.  *out_nvertices / *out_ntriangles are always set; PCPX_ERR_CAPACITY if either
+ * output is NULL or short (call again with room for the totals).  sx*sy*sz < 2^32 (else PCPX_ERR_INVALID); an empty grid
+ * gives an empty mesh.  Synchronises `stream`. */
+int pcpx_surface_nets_dev(const float* d_field, const pcpx_grid3d* grid, float isovalue, int device, void* stream, float* d_out_xyz,
+                          uint64_t vertex_capacity, uint32_t* d_out_tri, uint64_t triangle_capacity, uint64_t* out_nvertices,
+                          uint64_t* out_ntriangles);
+/* The same with device-event times of its three passes (flags + scan, map + vertices, triangle count + scan + write), ms. */
+int pcpx_surface_nets_timed_dev(const float* d_field, const pcpx_grid3d* grid, float isovalue, int device, void* stream, float* d_out_xyz,
+                                uint64_t vertex_capacity, uint32_t* d_out_tri, uint64_t triangle_capacity, uint64_t* out_nvertices,
+                                uint64_t* out_ntriangles, float out_pass_ms[3]);
+/* Host arrays. */
+int pcpx_surface_nets(const float* field, const pcpx_grid3d* grid, float isovalue, int device, float* out_xyz, uint64_t vertex_capacity,
+                      uint32_t* out_tri, uint64_t triangle_capacity, uint64_t* out_nvertices, uint64_t* out_ntriangles);
+/* The example's signed-distance function at every corner of `grid`: the nearest indexed point j of the corner (1-NN with the
+ * eps-box exclusion, as nearest_neighbours(coords, 1)) and dot(c - o_j, n_j) with the plane (o, n) of point j -- d_centroids,
+ * d_normals: n x 3 device arrays in input order, e.g. from pcpx_neighbourhoods_self_dev.  Corners outside the index's voxel
+ * grid are answered too.  A corner with no point outside its eps-box gets NaN.  Enqueued on the handle's stream, which it
+ * synchronises. */
+int pcpx_tangent_plane_sdf_dev(pcpx_index* idx, const float* d_centroids, const float* d_normals, const pcpx_grid3d* grid, float eps,
+                               float* d_out_field);
+/* Tangent-plane surface reconstruction in one call: k-nearest-neighbour tangent planes of every indexed point, their normals
+ * oriented by the device orientation pass, the grid regular_grid_containing(box of the index, dims), the field above and
+ * surface nets at `isovalue`; only counts cross to the host.  Outputs as pcpx_surface_nets_dev (a short buffer: the whole
+ * pipeline runs again on the second call); opt_out_centroids / opt_out_normals (n x 3, input order) receive the oriented
+ * planes, opt_out_grid the grid.  PCPX_ERR_UNSUPPORTED if points were dropped by an explicit voxel grid. */
+int pcpx_reconstruct_surface(pcpx_index* idx, uint32_t k, float eps, const uint64_t dims[3], float isovalue, float* out_xyz,
+                             uint64_t vertex_capacity, uint32_t* out_tri, uint64_t triangle_capacity, uint64_t* out_nvertices,
+                             uint64_t* out_ntriangles, float* opt_out_centroids, float* opt_out_normals, pcpx_grid3d* opt_out_grid);
+int pcpx_reconstruct_surface_dev(pcpx_index* idx, uint32_t k, float eps, const uint64_t dims[3], float isovalue, float* d_out_xyz,
+                                 uint64_t vertex_capacity, uint32_t* d_out_tri, uint64_t triangle_capacity, uint64_t* out_nvertices,
+                                 uint64_t* out_ntriangles, float* d_opt_out_centroids, float* d_opt_out_normals, pcpx_grid3d* opt_out_grid);
+
 #ifdef __cplusplus
 }
 #endif

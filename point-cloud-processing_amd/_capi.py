@@ -35,6 +35,12 @@ class Profile(C.Structure):
     _fields_ = [("launches", C.c_uint32 * 5), ("total_ms", C.c_float * 5)]
 
 
+class Grid3d(C.Structure):
+    """pcpx_grid3d ~ pcp::common::regular_grid3d_t<float>: origin, voxel size, voxels per axis."""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("dx", C.c_float), ("dy", C.c_float), ("dz", C.c_float),
+                ("sx", C.c_uint64), ("sy", C.c_uint64), ("sz", C.c_uint64)]
+
+
 K_BUILD, K_KNN, K_NORMALS, K_RANGE, K_QUERY_PREP = range(5)
 
 
@@ -138,6 +144,18 @@ SIGNATURES = {
     "pcpx_kd_size": (C.c_uint64, [C.c_void_p]),
     "pcpx_kd_dims": (C.c_uint32, [C.c_void_p]),
     "pcpx_kd_knn_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcpx_regular_grid_containing": (C.c_int, [f32p, f32p, u64p, C.POINTER(Grid3d)]),
+    "pcpx_surface_nets_dev": (C.c_int, [C.c_void_p, C.POINTER(Grid3d), C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                        C.c_uint64, u64p, u64p]),
+    "pcpx_surface_nets_timed_dev": (C.c_int, [C.c_void_p, C.POINTER(Grid3d), C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64,
+                                              C.c_void_p, C.c_uint64, u64p, u64p, f32p]),
+    "pcpx_surface_nets": (C.c_int, [C.c_void_p, C.POINTER(Grid3d), C.c_float, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                    u64p, u64p]),
+    "pcpx_tangent_plane_sdf_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Grid3d), C.c_float, C.c_void_p]),
+    "pcpx_reconstruct_surface": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, u64p, C.c_float, C.c_void_p, C.c_uint64, C.c_void_p,
+                                           C.c_uint64, u64p, u64p, C.c_void_p, C.c_void_p, C.POINTER(Grid3d)]),
+    "pcpx_reconstruct_surface_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, u64p, C.c_float, C.c_void_p, C.c_uint64, C.c_void_p,
+                                               C.c_uint64, u64p, u64p, C.c_void_p, C.c_void_p, C.POINTER(Grid3d)]),
     "pcpx_kd_range_aabb_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]),
 }
 

@@ -453,6 +453,17 @@ int launch_wlop_density(Index& ix, float h, const void* d_records, float* d_out)
 int launch_wlop_median(Index& cloud, const QueryView& samples, float h, const void* d_records_vj, float* d_median);
 int launch_wlop_repulsion(Index& samples, float h, float mu, const void* d_records_wi, const float* d_median, float* d_out);
 int prepare_queries(Index& ix, const float* d_q, u64 nq, QueryView& qv);
+// isosurface.hip: the tangent-plane distance field at the corners of a grid (one k = 1 query per corner through the index's
+// query path) and surface nets over a field.  surface_nets_device returns both totals always and PCPX_ERR_CAPACITY when an
+// output does not hold them (nothing of that output written); its scratch comes from `pool`, and it synchronises `s`.
+struct SurfaceNetsTimes {
+    float flags_ms = 0, vertices_ms = 0, triangles_ms = 0;  // pass 1 + scan, pass 2, pass 3 (count, scan, write)
+};
+int check_surface_grid(const pcpx_grid3d& grid);  // PCPX_ERR_INVALID unless sx*sy*sz < 2^32
+int tangent_plane_sdf_device(Index& ix, const float* d_centroids, const float* d_normals, const pcpx_grid3d& grid, float eps, float* d_field);
+int surface_nets_device(const float* d_field, const pcpx_grid3d& grid, float iso, hipStream_t s, DevPool& pool, float* d_out_xyz,
+                        u64 vertex_capacity, u32* d_out_tri, u64 triangle_capacity, u64* out_nv, u64* out_nt,
+                        SurfaceNetsTimes* times = nullptr);
 int launch_invert_perm(const u32* d_perm, u64 n, u32* d_position_of, hipStream_t s);
 int ensure_queue(Index& ix);   // the counters' allocation (zeroed)
 int sched_reserve(Index& ix, u64 groups);  // the arrays of the recorded order for launches of up to `groups` query groups (Index::sched)

@@ -1,0 +1,532 @@
+// pcpx_isosurface.hip -- tangent-plane surface reconstruction: the signed-distance field at the corners of a regular grid and
+// naive surface nets over it (include/pcp/algorithm/surface_nets.hpp:357-650 of the reference, the overload that marches
+// over the whole grid).
+//
+// Field: every grid corner is a kNN query (k = 1) through the index's query path; a small kernel turns the nearest point's
+// tangent plane into dot(c - o, n).  Corners are enumerated in 4x4x4 bricks, so the queries handed to the query sort arrive
+// spatially coherent.
+//
+// Surface nets, three passes with device scans and no atomics, so the output order is fixed:
+//   1. one thread per cube: active flag (some edge bipolar);  exclusive scan -> vertex index of every active cube, in
+//      ascending linear cube index i + j*sx + k*sx*sy;
+//   2. one thread per cube: dense cube -> vertex map (UINT32_MAX = inactive), list of active cubes, vertex position;
+//   3. one thread per active cube: triangle count;  scan;  the same thread again: the triangles, in (cube, quad 0..2,
+//      triangle 0..1) order.
+// The vertex arithmetic is the reference's operation for operation; the build's -ffp-contract=off keeps it unfused.
+#include "pcpx_internal.h"
+
+#include <algorithm>
+
+namespace pcpx {
+
+namespace {
+
+constexpr int SN_BLOCK = 256;
+constexpr u32 SN_MAX_BLOCKS = 8192;  // grid-stride beyond this: 256 CUs x 32 blocks of 256 threads cover the card many times over
+constexpr int SCAN_THREADS = 256, SCAN_ITEMS = 8, SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;
+constexpr u32 NO_VERTEX = 0xFFFFFFFFu;
+
+u32 blocks_for(u64 n)
+{
+    const u64 b = (n + SN_BLOCK - 1) / SN_BLOCK;
+    return static_cast<u32>(b < SN_MAX_BLOCKS ? (b > 0 ? b : 1) : SN_MAX_BLOCKS);
+}
+
+struct GridDev {
+    float x, y, z, dx, dy, dz;
+    u32 sx, sy, sz;  // cubes per axis; sx*sy*sz < 2^32
+};
+
+__device__ __forceinline__ u64 corner_at(const GridDev& g, u32 i, u32 j, u32 k)
+{
+    return static_cast<u64>(i) + static_cast<u64>(g.sx + 1) * (static_cast<u64>(j) + static_cast<u64>(g.sy + 1) * k);
+}
+
+// get_world_point_of (surface_nets.hpp:31-41)
+__device__ __forceinline__ float3 world_of(const GridDev& g, u32 i, u32 j, u32 k)
+{
+    return make_float3(g.x + static_cast<float>(i) * g.dx, g.y + static_cast<float>(j) * g.dy, g.z + static_cast<float>(k) * g.dz);
+}
+
+// ---- tangent-plane distance field ---------------------------------------------------------------------------------------
+
+struct Bricks {
+    u32 bx, by, bz;  // bricks per axis over the (sx+1) x (sy+1) x (sz+1) corners
+};
+
+// corner of brick-order query p (clamped into the grid for the padding of partial bricks; `inside` tells which)
+__device__ __forceinline__ void brick_corner(const GridDev& g, const Bricks& b, u64 p, u32& i, u32& j, u32& k, bool& inside)
+{
+    const u64 brick = p >> 6;
+    const u32 r = static_cast<u32>(p & 63u);
+    const u64 bxy = static_cast<u64>(b.bx) * b.by;
+    i = static_cast<u32>(brick % b.bx) * 4u + (r & 3u);
+    j = static_cast<u32>((brick / b.bx) % b.by) * 4u + ((r >> 2) & 3u);
+    k = static_cast<u32>(brick / bxy) * 4u + (r >> 4);
+    inside = i <= g.sx && j <= g.sy && k <= g.sz;
+    i = i <= g.sx ? i : g.sx;
+    j = j <= g.sy ? j : g.sy;
+    k = k <= g.sz ? k : g.sz;
+}
+
+__global__ __launch_bounds__(SN_BLOCK) void k_sdf_queries(GridDev g, Bricks b, u64 nq, float* __restrict__ q)
+{
+    for (u64 p = static_cast<u64>(blockIdx.x) * SN_BLOCK + threadIdx.x; p < nq; p += static_cast<u64>(gridDim.x) * SN_BLOCK) {
+        u32 i, j, k;
+        bool inside;
+        brick_corner(g, b, p, i, j, k, inside);
+        const float3 c = world_of(g, i, j, k);
+        q[3 * p] = c.x;
+        q[3 * p + 1] = c.y;
+        q[3 * p + 2] = c.z;
+    }
+}
+
+// field[corner] = inner_product(c - o, n) of the nearest point's plane (common/norm.hpp:34: n.x * op.x + ..., left to right);
+// NaN where no point is outside the eps-box of the corner (the reference would dereference an empty neighbour list)
+__global__ __launch_bounds__(SN_BLOCK) void k_sdf_eval(GridDev g, Bricks b, u64 nq, const u32* __restrict__ nn, const u32* __restrict__ cnt,
+                                                       const float* __restrict__ centroids, const float* __restrict__ normals,
+                                                       float* __restrict__ field)
+{
+    for (u64 p = static_cast<u64>(blockIdx.x) * SN_BLOCK + threadIdx.x; p < nq; p += static_cast<u64>(gridDim.x) * SN_BLOCK) {
+        u32 i, j, k;
+        bool inside;
+        brick_corner(g, b, p, i, j, k, inside);
+        if (!inside) continue;
+        float v = __builtin_nanf("");
+        if (cnt[p] > 0) {
+            const u64 o = nn[p];
+            const float3 c = world_of(g, i, j, k);
+            const float opx = c.x - centroids[3 * o], opy = c.y - centroids[3 * o + 1], opz = c.z - centroids[3 * o + 2];
+            const float xx = normals[3 * o] * opx, yy = normals[3 * o + 1] * opy, zz = normals[3 * o + 2] * opz;
+            v = xx + yy + zz;
+        }
+        field[corner_at(g, i, j, k)] = v;
+    }
+}
+
+// ---- exclusive scan, in place, over n entries (the caller's last entry is 0 and receives the total) ------------------------
+
+template <class T>
+__device__ T block_exclusive_scan(T v, T* lds, T& total)
+{
+    const int t = threadIdx.x;
+    lds[t] = v;
+    __syncthreads();
+    for (int off = 1; off < SCAN_THREADS; off <<= 1) {
+        const T add = t >= off ? lds[t - off] : T(0);
+        __syncthreads();
+        lds[t] += add;
+        __syncthreads();
+    }
+    const T incl = lds[t];
+    total = lds[SCAN_THREADS - 1];
+    __syncthreads();
+    return incl - v;
+}
+
+template <class T>
+__global__ __launch_bounds__(SCAN_THREADS) void k_scan_reduce(const T* __restrict__ a, u64 n, T* __restrict__ sums)
+{
+    __shared__ T lds[SCAN_THREADS];
+    const u64 base = static_cast<u64>(blockIdx.x) * SCAN_TILE;
+    T s = 0;
+    for (int r = 0; r < SCAN_ITEMS; ++r) {
+        const u64 e = base + static_cast<u64>(r) * SCAN_THREADS + threadIdx.x;
+        if (e < n) s += a[e];
+    }
+    T total;
+    (void)block_exclusive_scan<T>(s, lds, total);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+template <class T>
+__global__ __launch_bounds__(SCAN_THREADS) void k_scan_sums(T* __restrict__ sums, u64 ntiles)
+{
+    __shared__ T lds[SCAN_THREADS];
+    T carry = 0;
+    for (u64 base = 0; base < ntiles; base += SCAN_THREADS) {
+        const u64 e = base + threadIdx.x;
+        const T v = e < ntiles ? sums[e] : T(0);
+        T total;
+        const T ex = block_exclusive_scan<T>(v, lds, total);
+        if (e < ntiles) sums[e] = carry + ex;
+        carry += total;
+    }
+}
+
+template <class T>
+__global__ __launch_bounds__(SCAN_THREADS) void k_scan_apply(T* __restrict__ a, u64 n, const T* __restrict__ sums)
+{
+    __shared__ T tile[SCAN_TILE];
+    __shared__ T lds[SCAN_THREADS];
+    const u64 base = static_cast<u64>(blockIdx.x) * SCAN_TILE;
+    for (int r = 0; r < SCAN_ITEMS; ++r) {  // coalesced load into LDS
+        const int l = r * SCAN_THREADS + threadIdx.x;
+        tile[l] = base + l < n ? a[base + l] : T(0);
+    }
+    __syncthreads();
+    T mine[SCAN_ITEMS], s = 0;
+    for (int r = 0; r < SCAN_ITEMS; ++r) {  // thread t owns items [t*ITEMS, t*ITEMS + ITEMS) of the tile
+        mine[r] = s;
+        s += tile[threadIdx.x * SCAN_ITEMS + r];
+    }
+    T total;
+    const T ex = block_exclusive_scan<T>(s, lds, total) + sums[blockIdx.x];
+    for (int r = 0; r < SCAN_ITEMS; ++r) tile[threadIdx.x * SCAN_ITEMS + r] = ex + mine[r];
+    __syncthreads();
+    for (int r = 0; r < SCAN_ITEMS; ++r) {
+        const int l = r * SCAN_THREADS + threadIdx.x;
+        if (base + l < n) a[base + l] = tile[l];
+    }
+}
+
+template <class T>
+int exclusive_scan_in_place(T* d_a, u64 n, T* d_sums, hipStream_t s)
+{
+    const u64 tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
+    if (tiles == 0) return PCPX_OK;
+    if (tiles > 0x7FFFFFFFull) {
+        set_error("pcpx: scan of %llu entries is too long", static_cast<unsigned long long>(n));
+        return PCPX_ERR_INVALID;
+    }
+    k_scan_reduce<T><<<static_cast<u32>(tiles), SCAN_THREADS, 0, s>>>(d_a, n, d_sums);
+    k_scan_sums<T><<<1, SCAN_THREADS, 0, s>>>(d_sums, tiles);
+    k_scan_apply<T><<<static_cast<u32>(tiles), SCAN_THREADS, 0, s>>>(d_a, n, d_sums);
+    PCPX_HIP(hipGetLastError());
+    return PCPX_OK;
+}
+
+// ---- surface nets -------------------------------------------------------------------------------------------------------
+
+// the reference's `edges` table (surface_nets.hpp:453-465) over the corner order of get_voxel_corner_grid_positions
+__constant__ unsigned char c_edges[12][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 0}, {4, 5}, {5, 6}, {6, 7}, {7, 4}, {0, 4}, {1, 5}, {2, 6}, {3, 7}};
+
+__device__ __forceinline__ void cube_of(const GridDev& g, u32 c, u32& i, u32& j, u32& k)
+{
+    i = c % g.sx;
+    j = (c / g.sx) % g.sy;
+    k = c / (g.sx * g.sy);
+}
+
+__device__ __forceinline__ void cube_corners(const GridDev& g, const float* __restrict__ f, u32 i, u32 j, u32 k, float s[8])
+{
+    const u64 X = g.sx + 1u, XY = X * (g.sy + 1u);
+    const u64 c0 = corner_at(g, i, j, k);
+    s[0] = f[c0];
+    s[1] = f[c0 + 1];
+    s[2] = f[c0 + 1 + X];
+    s[3] = f[c0 + X];
+    s[4] = f[c0 + XY];
+    s[5] = f[c0 + 1 + XY];
+    s[6] = f[c0 + 1 + X + XY];
+    s[7] = f[c0 + X + XY];
+}
+
+// active iff some edge is bipolar; the 12 edges connect all 8 corners, so: iff the corners are not all on one side
+__device__ __forceinline__ bool cube_active(const float s[8], float iso)
+{
+    const bool p0 = s[0] >= iso;
+    bool mixed = false;
+#pragma unroll
+    for (int q = 1; q < 8; ++q) mixed |= (s[q] >= iso) != p0;
+    return mixed;
+}
+
+__global__ __launch_bounds__(SN_BLOCK) void k_sn_flags(GridDev g, u32 ncubes, const float* __restrict__ field, float iso,
+                                                       u32* __restrict__ flag)
+{
+    for (u64 c64 = static_cast<u64>(blockIdx.x) * SN_BLOCK + threadIdx.x; c64 < ncubes; c64 += static_cast<u64>(gridDim.x) * SN_BLOCK) {
+        const u32 c = static_cast<u32>(c64);
+        u32 i, j, k;
+        cube_of(g, c, i, j, k);
+        float s[8];
+        cube_corners(g, field, i, j, k, s);
+        flag[c] = cube_active(s, iso) ? 1u : 0u;
+    }
+}
+
+// the mesh vertex of an active cube (surface_nets.hpp:467-519): centroid of the edge crossings in grid coordinates, then
+// mapped into mesh_aabb
+__device__ __forceinline__ float3 cube_vertex(const GridDev& g, u32 i, u32 j, u32 k, const float s[8], float iso)
+{
+    const float fi = static_cast<float>(i), fj = static_cast<float>(j), fk = static_cast<float>(k);
+    const float fi1 = fi + 1.f, fj1 = fj + 1.f, fk1 = fk + 1.f;
+    const float px[8] = {fi, fi1, fi1, fi, fi, fi1, fi1, fi};
+    const float py[8] = {fj, fj, fj1, fj1, fj, fj, fj1, fj1};
+    const float pz[8] = {fk, fk, fk, fk, fk1, fk1, fk1, fk1};
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    int n = 0;
+#pragma unroll
+    for (int e = 0; e < 12; ++e) {
+        const int a = c_edges[e][0], b = c_edges[e][1];
+        if ((s[a] >= iso) == (s[b] >= iso)) continue;
+        const float t = (iso - s[a]) / (s[b] - s[a]);
+        // p1 + t * (p2 - p1), then accumulated from point_type{} (vector3d_queries.hpp:79-99)
+        sx = sx + (px[a] + t * (px[b] - px[a]));
+        sy = sy + (py[a] + t * (py[b] - py[a]));
+        sz = sz + (pz[a] + t * (pz[b] - pz[a]));
+        ++n;
+    }
+    const float fn = static_cast<float>(n);
+    const float cx = sx / fn, cy = sy / fn, cz = sz / fn;
+    // mesh_aabb = {get_world_point_of(0, 0, 0), get_world_point_of(sx, sy, sz)}
+    const float minx = g.x + 0.f * g.dx, miny = g.y + 0.f * g.dy, minz = g.z + 0.f * g.dz;
+    const float maxx = g.x + static_cast<float>(g.sx) * g.dx, maxy = g.y + static_cast<float>(g.sy) * g.dy,
+                maxz = g.z + static_cast<float>(g.sz) * g.dz;
+    return make_float3(minx + (maxx - minx) * (cx - 0.f) / (static_cast<float>(g.sx) - 0.f),
+                       miny + (maxy - miny) * (cy - 0.f) / (static_cast<float>(g.sy) - 0.f),
+                       minz + (maxz - minz) * (cz - 0.f) / (static_cast<float>(g.sz) - 0.f));
+}
+
+// vofs: the exclusive scan of the flags (ncubes + 1 entries); an active cube c has vofs[c + 1] != vofs[c]
+__global__ __launch_bounds__(SN_BLOCK) void k_sn_vertices(GridDev g, u32 ncubes, const float* __restrict__ field, float iso,
+                                                          const u32* __restrict__ vofs, u32* __restrict__ map, u32* __restrict__ active,
+                                                          float* __restrict__ out_xyz)
+{
+    for (u64 c64 = static_cast<u64>(blockIdx.x) * SN_BLOCK + threadIdx.x; c64 < ncubes; c64 += static_cast<u64>(gridDim.x) * SN_BLOCK) {
+        const u32 c = static_cast<u32>(c64);
+        const u32 v = vofs[c];
+        const bool on = vofs[c + 1] != v;
+        map[c] = on ? v : NO_VERTEX;
+        if (!on) continue;
+        active[v] = c;
+        if (!out_xyz) continue;
+        u32 i, j, k;
+        cube_of(g, c, i, j, k);
+        float s[8];
+        cube_corners(g, field, i, j, k, s);
+        const float3 p = cube_vertex(g, i, j, k, s, iso);
+        out_xyz[3ull * v] = p.x;
+        out_xyz[3ull * v + 1] = p.y;
+        out_xyz[3ull * v + 2] = p.z;
+    }
+}
+
+// neighbours of cube (i, j, k) in the reference's order (surface_nets.hpp:549-556) and the three quads over them (:586)
+__device__ __forceinline__ void quad_vertices(const GridDev& g, const u32* __restrict__ map, u32 i, u32 j, u32 k, u32 nv[3][3])
+{
+    const u32 sx = g.sx, sxy = g.sx * g.sy;
+    const u32 c = i + j * sx + k * sxy;
+    const u32 n0 = map[c - 1], n1 = map[c - 1 - sx], n2 = map[c - sx], n3 = map[c - sx - sxy], n4 = map[c - sxy], n5 = map[c - 1 - sxy];
+    nv[0][0] = n0, nv[0][1] = n1, nv[0][2] = n2;
+    nv[1][0] = n0, nv[1][1] = n5, nv[1][2] = n4;
+    nv[2][0] = n2, nv[2][1] = n3, nv[2][2] = n4;
+}
+
+__global__ __launch_bounds__(SN_BLOCK) void k_sn_tri_count(GridDev g, u32 nvert, const u32* __restrict__ active, const u32* __restrict__ map,
+                                                           u64* __restrict__ tcnt)
+{
+    for (u64 v64 = static_cast<u64>(blockIdx.x) * SN_BLOCK + threadIdx.x; v64 < nvert; v64 += static_cast<u64>(gridDim.x) * SN_BLOCK) {
+        const u32 v = static_cast<u32>(v64);
+        u32 i, j, k;
+        cube_of(g, active[v], i, j, k);
+        u64 t = 0;
+        if (i > 0 && j > 0 && k > 0) {
+            u32 nv[3][3];
+            quad_vertices(g, map, i, j, k, nv);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) t += (nv[q][0] != NO_VERTEX && nv[q][1] != NO_VERTEX && nv[q][2] != NO_VERTEX) ? 2u : 0u;
+        }
+        tcnt[v] = t;
+    }
+}
+
+__global__ __launch_bounds__(SN_BLOCK) void k_sn_triangles(GridDev g, u32 nvert, const float* __restrict__ field, const u32* __restrict__ active,
+                                                           const u32* __restrict__ map, const u64* __restrict__ tofs, u32* __restrict__ out_tri)
+{
+    for (u64 v64 = static_cast<u64>(blockIdx.x) * SN_BLOCK + threadIdx.x; v64 < nvert; v64 += static_cast<u64>(gridDim.x) * SN_BLOCK) {
+        const u32 v = static_cast<u32>(v64);
+        u64 t = tofs[v64];
+        if (tofs[v64 + 1] == t) continue;
+        u32 i, j, k;
+        cube_of(g, active[v], i, j, k);
+        u32 nv[3][3];
+        quad_vertices(g, map, i, j, k, nv);
+        // the directed edges (0,4), (3,0), (0,1) of the cube (surface_nets.hpp:558-584)
+        const float s0 = field[corner_at(g, i, j, k)], s4 = field[corner_at(g, i, j, k + 1)], s3 = field[corner_at(g, i, j + 1, k)],
+                    s1 = field[corner_at(g, i + 1, j, k)];
+        const float e0[3] = {s0, s3, s0}, e1[3] = {s4, s0, s1};
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            if (nv[q][0] == NO_VERTEX || nv[q][1] == NO_VERTEX || nv[q][2] == NO_VERTEX) continue;
+            const bool fwd = e1[q] > e0[q];
+            const u32 v1 = fwd ? nv[q][0] : nv[q][2], v2 = nv[q][1], v3 = fwd ? nv[q][2] : nv[q][0];
+            u32* o = out_tri + 3 * t;
+            o[0] = v, o[1] = v1, o[2] = v2;
+            o[3] = v, o[4] = v2, o[5] = v3;
+            t += 2;
+        }
+    }
+}
+
+// a block of the caller's pool, returned on scope exit
+struct PoolBuf {
+    DevPool& pool;
+    void* p = nullptr;
+    explicit PoolBuf(DevPool& owner) : pool(owner) {}
+    PoolBuf(const PoolBuf&) = delete;
+    PoolBuf& operator=(const PoolBuf&) = delete;
+    ~PoolBuf()
+    {
+        if (p) pool.release(p);
+    }
+    int alloc(size_t bytes)
+    {
+        p = pool.acquire(bytes > 0 ? bytes : 16);
+        return p ? PCPX_OK : PCPX_ERR_ALLOC;
+    }
+    template <class T>
+    T* as() const { return static_cast<T*>(p); }
+};
+
+int grid_to_dev(const pcpx_grid3d& g, GridDev& d, u64& ncubes)
+{
+    ncubes = 0;
+    if (g.sx == 0 || g.sy == 0 || g.sz == 0) return PCPX_OK;
+    const u64 lim = 0xFFFFFFFFull;
+    if (g.sx >= lim || g.sy >= lim || g.sz >= lim || g.sx * g.sy >= lim || g.sx * g.sy * g.sz >= lim) {
+        set_error("pcpx: grid of %llu x %llu x %llu cubes: sx * sy * sz must be below 2^32", static_cast<unsigned long long>(g.sx),
+                  static_cast<unsigned long long>(g.sy), static_cast<unsigned long long>(g.sz));
+        return PCPX_ERR_INVALID;
+    }
+    d = GridDev{g.x, g.y, g.z, g.dx, g.dy, g.dz, static_cast<u32>(g.sx), static_cast<u32>(g.sy), static_cast<u32>(g.sz)};
+    ncubes = g.sx * g.sy * g.sz;
+    return PCPX_OK;
+}
+
+}  // namespace
+
+int check_surface_grid(const pcpx_grid3d& grid)
+{
+    GridDev g{};
+    u64 ncubes = 0;
+    return grid_to_dev(grid, g, ncubes);
+}
+
+int surface_nets_device(const float* d_field, const pcpx_grid3d& grid, float iso, hipStream_t s, DevPool& pool, float* d_out_xyz,
+                        u64 vertex_capacity, u32* d_out_tri, u64 triangle_capacity, u64* out_nv, u64* out_nt, SurfaceNetsTimes* times)
+{
+    *out_nv = 0;
+    *out_nt = 0;
+    GridDev g{};
+    u64 ncubes = 0;
+    int st = grid_to_dev(grid, g, ncubes);
+    if (st != PCPX_OK || ncubes == 0) return st;
+    if (!d_field) {
+        set_error("pcpx_surface_nets_dev: null field");
+        return PCPX_ERR_INVALID;
+    }
+    const u32 nc = static_cast<u32>(ncubes);
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (times) {
+        for (auto& e : ev) PCPX_HIP(hipEventCreate(&e));
+    }
+    struct EventsGone {
+        hipEvent_t* e;
+        ~EventsGone()
+        {
+            for (int q = 0; q < 4; ++q)
+                if (e[q]) (void)hipEventDestroy(e[q]);
+        }
+    } events_gone{ev};
+    // pass 1: flags, scanned in place into vertex offsets (ncubes + 1 entries)
+    PoolBuf vofs(pool), sums(pool), map(pool);
+    const u64 tiles_c = (ncubes + 1 + SCAN_TILE - 1) / SCAN_TILE;
+    if ((st = vofs.alloc((ncubes + 1) * sizeof(u32))) != PCPX_OK || (st = map.alloc(ncubes * sizeof(u32))) != PCPX_OK ||
+        (st = sums.alloc(std::max<u64>(tiles_c, 64) * sizeof(u64))) != PCPX_OK)
+        return st;
+    if (times) PCPX_HIP(hipEventRecord(ev[0], s));
+    PCPX_HIP(hipMemsetAsync(vofs.as<u32>() + ncubes, 0, sizeof(u32), s));
+    k_sn_flags<<<blocks_for(ncubes), SN_BLOCK, 0, s>>>(g, nc, d_field, iso, vofs.as<u32>());
+    PCPX_HIP(hipGetLastError());
+    if ((st = exclusive_scan_in_place<u32>(vofs.as<u32>(), ncubes + 1, sums.as<u32>(), s)) != PCPX_OK) return st;
+    if (times) PCPX_HIP(hipEventRecord(ev[1], s));
+    u32 nv32 = 0;
+    PCPX_HIP(hipMemcpyAsync(&nv32, vofs.as<u32>() + ncubes, sizeof(u32), hipMemcpyDeviceToHost, s));
+    PCPX_HIP(hipStreamSynchronize(s));
+    const u64 nv = nv32;
+    *out_nv = nv;
+    // pass 2: the map, the active cubes, and the vertices if they fit
+    PoolBuf active(pool), tofs(pool), tsums(pool);
+    const u64 tiles_v = (nv + 1 + SCAN_TILE - 1) / SCAN_TILE;
+    if ((st = active.alloc(nv * sizeof(u32))) != PCPX_OK || (st = tofs.alloc((nv + 1) * sizeof(u64))) != PCPX_OK ||
+        (st = tsums.alloc(std::max<u64>(tiles_v, 64) * sizeof(u64))) != PCPX_OK)
+        return st;
+    const bool write_vertices = d_out_xyz && nv <= vertex_capacity;
+    k_sn_vertices<<<blocks_for(ncubes), SN_BLOCK, 0, s>>>(g, nc, d_field, iso, vofs.as<u32>(), map.as<u32>(), active.as<u32>(),
+                                                          write_vertices ? d_out_xyz : nullptr);
+    PCPX_HIP(hipGetLastError());
+    if (times) PCPX_HIP(hipEventRecord(ev[2], s));
+    // pass 3: triangle counts of the active cubes, scanned; then the triangles if they fit
+    u64 nt = 0;
+    if (nv > 0) {
+        PCPX_HIP(hipMemsetAsync(tofs.as<u64>() + nv, 0, sizeof(u64), s));
+        k_sn_tri_count<<<blocks_for(nv), SN_BLOCK, 0, s>>>(g, nv32, active.as<u32>(), map.as<u32>(), tofs.as<u64>());
+        PCPX_HIP(hipGetLastError());
+        if ((st = exclusive_scan_in_place<u64>(tofs.as<u64>(), nv + 1, tsums.as<u64>(), s)) != PCPX_OK) return st;
+        PCPX_HIP(hipMemcpyAsync(&nt, tofs.as<u64>() + nv, sizeof(u64), hipMemcpyDeviceToHost, s));
+        PCPX_HIP(hipStreamSynchronize(s));
+    }
+    *out_nt = nt;
+    const bool write_triangles = d_out_tri && nt <= triangle_capacity;
+    if (nt > 0 && write_triangles) {
+        k_sn_triangles<<<blocks_for(nv), SN_BLOCK, 0, s>>>(g, nv32, d_field, active.as<u32>(), map.as<u32>(), tofs.as<u64>(), d_out_tri);
+        PCPX_HIP(hipGetLastError());
+    }
+    if (times) {
+        PCPX_HIP(hipEventRecord(ev[3], s));
+        PCPX_HIP(hipEventSynchronize(ev[3]));
+        PCPX_HIP(hipEventElapsedTime(&times->flags_ms, ev[0], ev[1]));
+        PCPX_HIP(hipEventElapsedTime(&times->vertices_ms, ev[1], ev[2]));
+        PCPX_HIP(hipEventElapsedTime(&times->triangles_ms, ev[2], ev[3]));
+    }
+    // the scratch goes back to the pool on return: nothing that reads it may still be queued
+    PCPX_HIP(hipStreamSynchronize(s));
+    if ((nv > 0 && !write_vertices) || (nt > 0 && !write_triangles)) {
+        set_error("pcpx_surface_nets: the mesh has %llu vertices and %llu triangles", static_cast<unsigned long long>(nv),
+                  static_cast<unsigned long long>(nt));
+        return PCPX_ERR_CAPACITY;
+    }
+    return PCPX_OK;
+}
+
+int tangent_plane_sdf_device(Index& ix, const float* d_centroids, const float* d_normals, const pcpx_grid3d& grid, float eps, float* d_field)
+{
+    GridDev g{};
+    u64 ncubes = 0;
+    int st = grid_to_dev(grid, g, ncubes);
+    if (st != PCPX_OK) return st;
+    // (a grid with no cube along some axis still has corners: the field is defined there too)
+    g.x = grid.x, g.y = grid.y, g.z = grid.z, g.dx = grid.dx, g.dy = grid.dy, g.dz = grid.dz;
+    g.sx = static_cast<u32>(grid.sx), g.sy = static_cast<u32>(grid.sy), g.sz = static_cast<u32>(grid.sz);
+    const Bricks b{static_cast<u32>((grid.sx + 1 + 3) / 4), static_cast<u32>((grid.sy + 1 + 3) / 4), static_cast<u32>((grid.sz + 1 + 3) / 4)};
+    const u64 nq = static_cast<u64>(b.bx) * b.by * b.bz * 64;
+    if (nq >= 0xFFFFFFFEull) {
+        set_error("pcpx_tangent_plane_sdf_dev: %llu corner queries (4x4x4 bricks) do not fit 32-bit rows", static_cast<unsigned long long>(nq));
+        return PCPX_ERR_UNSUPPORTED;
+    }
+    if (ix.n == 0) {
+        set_error("pcpx_tangent_plane_sdf_dev: the index holds no points");
+        return PCPX_ERR_INVALID;
+    }
+    hipStream_t s = ix.stream;
+    PoolBuf q(ix.pool), nn(ix.pool), cnt(ix.pool);
+    if ((st = q.alloc(nq * 3 * sizeof(float))) != PCPX_OK || (st = nn.alloc(nq * sizeof(u32))) != PCPX_OK ||
+        (st = cnt.alloc(nq * sizeof(u32))) != PCPX_OK)
+        return st;
+    k_sdf_queries<<<blocks_for(nq), SN_BLOCK, 0, s>>>(g, b, nq, q.as<float>());
+    PCPX_HIP(hipGetLastError());
+    QueryView qv;
+    if ((st = prepare_queries(ix, q.as<float>(), nq, qv)) != PCPX_OK) return st;
+    KnnOutputs o;
+    o.idx = nn.as<u32>();
+    o.cnt = cnt.as<u32>();
+    if ((st = launch_knn(ix, qv, false, 0, (nq + GROUP - 1) / GROUP, 1, eps, o)) != PCPX_OK) return st;
+    k_sdf_eval<<<blocks_for(nq), SN_BLOCK, 0, s>>>(g, b, nq, nn.as<u32>(), cnt.as<u32>(), d_centroids, d_normals, d_field);
+    PCPX_HIP(hipGetLastError());
+    PCPX_HIP(hipStreamSynchronize(s));  // (the query buffers go back to the pool)
+    return PCPX_OK;
+}
+
+}  // namespace pcpx

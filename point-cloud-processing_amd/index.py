@@ -249,6 +249,17 @@ class Index:
         check(self._lib.pcpx_tangent_planes_knn_self(self._h, k, eps, _vp(cen), _vp(nrm)))
         return cen, nrm
 
+    def tangent_plane_sdf(self, centroids, normals, grid, eps=1e-5):
+        """The tangent-plane signed distance at every corner of `grid` (surface.tangent_plane_sdf)."""
+        from . import surface
+        return surface.tangent_plane_sdf(self, centroids, normals, grid, eps)
+
+    def reconstruct_surface(self, k, dims, eps=1e-5, isovalue=0.0, want_planes=False):
+        """Tangent-plane surface reconstruction in one call: (vertices (V,3) float32, triangles (T,3) uint32)
+        (surface.reconstruct_surface)."""
+        from . import surface
+        return surface.reconstruct_surface(self, k, dims, eps, isovalue, want_planes)
+
     def mean_knn_distance_self(self, k, eps=1e-5):
         """pcp::algorithm::average_distances_to_neighbors: mean distance to the k nearest neighbours, per point."""
         out = np.empty(self.n_in, np.float32)
