@@ -6,6 +6,7 @@
 #include "pcp/algorithm/bilateral_filter.hpp"
 #include "pcp/algorithm/estimate_normals.hpp"
 #include "pcp/algorithm/estimate_tangent_planes.hpp"
+#include "pcp/algorithm/hierarchy_simplification.hpp"
 #include "pcp/algorithm/surface_nets.hpp"
 #include "pcp/algorithm/wlop.hpp"
 #endif

@@ -498,6 +498,30 @@ int pcpx_reconstruct_surface_dev(pcpx_index* idx, uint32_t k, float eps, const u
                                  uint64_t vertex_capacity, uint32_t* d_out_tri, uint64_t triangle_capacity, uint64_t* out_nvertices,
                                  uint64_t* out_ntriangles, float* d_opt_out_centroids, float* d_opt_out_normals, pcpx_grid3d* opt_out_grid);
 
+/* ---- hierarchy simplification: replaces pcp::algorithm::hierarchy_simplification --------------------------------------
+ * (include/pcp/algorithm/hierarchy_simplification.hpp) ---------------------------------------------------------------------- */
+typedef struct pcpx_hierarchy_params {
+    uint32_t struct_size;  /* = sizeof(pcpx_hierarchy_params) */
+    uint64_t cluster_size; /* a cluster of more points than this is split; > 0 */
+    double var_max;        /* a cluster whose variation lambda0 / (lambda0 + lambda1 + lambda2) exceeds (float)var_max is split; >= 0 */
+} pcpx_hierarchy_params;
+/* Hierarchy simplification (Pauly et al.): starting from the whole cloud, a cluster of N points with mean mu is split by the
+ * plane through mu normal to its largest eigenvector n (f = p.n - mu.n <= 0: first child) while N > cluster_size or its
+ * variation exceeds var_max; otherwise the point nearest to mu is kept.  The kept points come out in the reference's queue
+ * order (breadth first, first child before second).  Contract: the mean, the centred scatter sums, the
+ * eigen solve, the variation and f are computed in double; n has its component of largest magnitude positive (the first on
+ * a tie); the partition keeps input order; the nearest point is the smallest input index on equal squared distance; a split
+ * that would leave one side empty makes the cluster a leaf instead (the reference loops forever there); a NaN variation
+ * (an all-zero scatter) does not split.  Deterministic.  out_xyz: K x 3 floats; opt_out_idx (may be NULL): the input index
+ * of every kept point.  *out_count is always set (K <= n); PCPX_ERR_CAPACITY if out_xyz is NULL or capacity < K (nothing
+ * written).  PCPX_ERR_INVALID for cluster_size 0, var_max < 0 or NaN, a non-finite coordinate (checked on the device), or
+ * n >= 2^32 - 1.  n == 0 keeps nothing. */
+int pcpx_hierarchy_simplification(const float* xyz, uint64_t n, const pcpx_hierarchy_params* params, int device, float* out_xyz,
+                                  uint32_t* opt_out_idx, uint64_t capacity, uint64_t* out_count);
+/* The same on device arrays, enqueued on `stream`, which it synchronises (it reads counts every level). */
+int pcpx_hierarchy_simplification_dev(const float* d_xyz, uint64_t n, const pcpx_hierarchy_params* params, int device, void* stream,
+                                      float* d_out_xyz, uint32_t* d_opt_out_idx, uint64_t capacity, uint64_t* out_count);
+
 #ifdef __cplusplus
 }
 #endif

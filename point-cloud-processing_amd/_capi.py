@@ -41,6 +41,11 @@ class Grid3d(C.Structure):
                 ("sx", C.c_uint64), ("sy", C.c_uint64), ("sz", C.c_uint64)]
 
 
+class HierarchyParams(C.Structure):
+    """pcpx_hierarchy_params ~ pcp::algorithm::hierarchy::params_t (struct_size first)."""
+    _fields_ = [("struct_size", C.c_uint32), ("cluster_size", C.c_uint64), ("var_max", C.c_double)]
+
+
 K_BUILD, K_KNN, K_NORMALS, K_RANGE, K_QUERY_PREP = range(5)
 
 
@@ -157,6 +162,10 @@ SIGNATURES = {
     "pcpx_reconstruct_surface_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, u64p, C.c_float, C.c_void_p, C.c_uint64, C.c_void_p,
                                                C.c_uint64, u64p, u64p, C.c_void_p, C.c_void_p, C.POINTER(Grid3d)]),
     "pcpx_kd_range_aabb_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "pcpx_hierarchy_simplification": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(HierarchyParams), C.c_int, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                u64p]),
+    "pcpx_hierarchy_simplification_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(HierarchyParams), C.c_int, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_uint64, u64p]),
 }
 
 _lib = None

@@ -2578,4 +2578,81 @@ int pcpx_reconstruct_surface(pcpx_index* h, uint32_t k, float eps, const uint64_
     });
 }
 
+static int hierarchy_params_of(const pcpx_hierarchy_params* params, u64& cluster_size, double& var_max)
+{
+    if (!params || params->struct_size != sizeof(pcpx_hierarchy_params)) {
+        set_error("pcpx_hierarchy_simplification: params missing or params->struct_size mismatch");
+        return PCPX_ERR_INVALID;
+    }
+    cluster_size = params->cluster_size;
+    var_max = params->var_max;
+    if (cluster_size == 0 || !(var_max >= 0.0)) {
+        set_error("pcpx_hierarchy_simplification: cluster_size must be > 0 and var_max >= 0 (not NaN)");
+        return PCPX_ERR_INVALID;
+    }
+    return PCPX_OK;
+}
+
+int pcpx_hierarchy_simplification_dev(const float* d_xyz, uint64_t n, const pcpx_hierarchy_params* params, int device, void* stream,
+                                      float* d_out_xyz, uint32_t* d_opt_out_idx, uint64_t capacity, uint64_t* out_count)
+{
+    if (!out_count) return PCPX_ERR_INVALID;
+    *out_count = 0;
+    u64 cluster_size = 0;
+    double var_max = 0;
+    int st = hierarchy_params_of(params, cluster_size, var_max);
+    if (st != PCPX_OK) return st;
+    DeviceScope dscope;
+    if ((st = dscope.select(device)) != PCPX_OK) return st;
+    return no_throw("pcpx_hierarchy_simplification_dev", [&]() -> int {
+        DeviceShared& sh = shared_of(device);
+        std::lock_guard<std::mutex> lock(sh.mu);
+        return hierarchy_device(d_xyz, n, cluster_size, var_max, static_cast<hipStream_t>(stream), sh.pool, d_out_xyz, d_opt_out_idx, capacity,
+                                out_count);
+    });
+}
+
+int pcpx_hierarchy_simplification(const float* xyz, uint64_t n, const pcpx_hierarchy_params* params, int device, float* out_xyz,
+                                  uint32_t* opt_out_idx, uint64_t capacity, uint64_t* out_count)
+{
+    if (!out_count) return PCPX_ERR_INVALID;
+    *out_count = 0;
+    u64 cluster_size = 0;
+    double var_max = 0;
+    int st = hierarchy_params_of(params, cluster_size, var_max);
+    if (st != PCPX_OK) return st;
+    if (n == 0) return PCPX_OK;
+    if (!xyz || n >= 0xFFFFFFFFull) {
+        set_error("pcpx_hierarchy_simplification: null points or more than 2^32 - 2 of them");
+        return PCPX_ERR_INVALID;
+    }
+    DeviceScope dscope;
+    if ((st = dscope.select(device)) != PCPX_OK) return st;
+    return no_throw("pcpx_hierarchy_simplification", [&]() -> int {
+        DeviceShared& sh = shared_of(device);
+        std::lock_guard<std::mutex> lock(sh.mu);
+        hipStream_t s = nullptr;
+        PCPX_HIP(pooled_stream_get(&s));
+        struct StreamBack {
+            hipStream_t s;
+            ~StreamBack() { pooled_stream_put(s); }
+        } back{s};
+        const u64 cap = out_xyz ? std::min<u64>(capacity, n) : 0;
+        DevBuf dp(sh.pool), dv(sh.pool), di(sh.pool);
+        int r;
+        if ((r = dp.alloc(n * 3 * sizeof(float))) != PCPX_OK || (cap > 0 && (r = dv.alloc(cap * 3 * sizeof(float))) != PCPX_OK) ||
+            (cap > 0 && opt_out_idx && (r = di.alloc(cap * sizeof(u32))) != PCPX_OK))
+            return r;
+        if ((r = upload_pageable(dp.p, xyz, n * 3 * sizeof(float), s)) != PCPX_OK) return r;
+        r = hierarchy_device(dp.as<float>(), n, cluster_size, var_max, s, sh.pool, cap > 0 ? dv.as<float>() : nullptr, di.as<u32>(), cap, out_count);
+        if (r != PCPX_OK) return r;
+        if (*out_count) {
+            PCPX_HIP(hipMemcpyAsync(out_xyz, dv.p, *out_count * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+            if (opt_out_idx) PCPX_HIP(hipMemcpyAsync(opt_out_idx, di.p, *out_count * sizeof(u32), hipMemcpyDeviceToHost, s));
+        }
+        PCPX_HIP(hipStreamSynchronize(s));
+        return PCPX_OK;
+    });
+}
+
 }  // extern "C"

@@ -464,6 +464,15 @@ int tangent_plane_sdf_device(Index& ix, const float* d_centroids, const float* d
 int surface_nets_device(const float* d_field, const pcpx_grid3d& grid, float iso, hipStream_t s, DevPool& pool, float* d_out_xyz,
                         u64 vertex_capacity, u32* d_out_tri, u64 triangle_capacity, u64* out_nv, u64* out_nt,
                         SurfaceNetsTimes* times = nullptr);
+// simplify.hip: hierarchy simplification of n points (device array, n x 3) level by level.  Always sets *out_count (the points
+// kept); PCPX_ERR_CAPACITY when d_out_xyz is null or holds fewer than that (nothing written); PCPX_ERR_INVALID for
+// cluster_size 0, var_max < 0 or NaN, a non-finite coordinate, or n >= 2^32 - 1.  Scratch from `pool`; synchronises `s`.
+struct HierarchyTimes {
+    float levels_ms = 0, gather_ms = 0;  // input check + every level, output gather
+    int levels = 0;
+};
+int hierarchy_device(const float* d_xyz, u64 n, u64 cluster_size, double var_max, hipStream_t s, DevPool& pool, float* d_out_xyz, u32* d_out_idx,
+                     u64 capacity, u64* out_count, HierarchyTimes* times = nullptr);
 int launch_invert_perm(const u32* d_perm, u64 n, u32* d_position_of, hipStream_t s);
 int ensure_queue(Index& ix);   // the counters' allocation (zeroed)
 int sched_reserve(Index& ix, u64 groups);  // the arrays of the recorded order for launches of up to `groups` query groups (Index::sched)
