@@ -105,20 +105,6 @@ int make_comm(ncclComm_t c, bool owned, int world, int rank, int device, Comm** 
     return PCPX_OK;
 }
 
-struct DeviceGuard {  // make `device` current for the call, restore the caller's on return
-    int prev = -1;
-    explicit DeviceGuard(int device)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != device) (void)hipSetDevice(device);
-        else prev = -1;
-    }
-    ~DeviceGuard()
-    {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
 }  // namespace
 }  // namespace pcpx
 
@@ -130,12 +116,14 @@ int pcpx_comm_unique_id(char out_id[PCPX_COMM_ID_BYTES])
 {
     static_assert(PCPX_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "id size");
     if (!out_id) return PCPX_ERR_INVALID;
+    return on_host("pcpx_comm_unique_id", [&]() -> int {
     int st = need_rccl();
     if (st != PCPX_OK) return st;
     ncclUniqueId id;
     if ((st = check_nccl(rccl().GetUniqueId(&id), "ncclGetUniqueId")) != PCPX_OK) return st;
     std::memcpy(out_id, id.internal, NCCL_UNIQUE_ID_BYTES);
     return PCPX_OK;
+    });
 }
 
 int pcpx_comm_init_rank(const char id[PCPX_COMM_ID_BYTES], int world, int rank, int device, pcpx_comm** out)
@@ -144,13 +132,7 @@ int pcpx_comm_init_rank(const char id[PCPX_COMM_ID_BYTES], int world, int rank, 
     *out = nullptr;
     int st = need_rccl();
     if (st != PCPX_OK) return st;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) {
-        (void)hipGetLastError();
-        set_error("pcpx_comm_init_rank: device %d is not available", device);
-        return PCPX_ERR_DEVICE;
-    }
-    DeviceGuard guard(device);
+    return on_device(device, "pcpx_comm_init_rank", [&]() -> int {
     ncclUniqueId uid;
     std::memcpy(uid.internal, id, NCCL_UNIQUE_ID_BYTES);
     ncclComm_t c = nullptr;
@@ -162,6 +144,7 @@ int pcpx_comm_init_rank(const char id[PCPX_COMM_ID_BYTES], int world, int rank, 
     }
     *out = reinterpret_cast<pcpx_comm*>(cm);
     return PCPX_OK;
+    }, PCPX_ERR_DEVICE);  // (a communicator's device out of range is PCPX_ERR_DEVICE)
 }
 
 int pcpx_comm_wrap(void* nccl_comm, int world, int rank, int device, pcpx_comm** out)
@@ -170,24 +153,20 @@ int pcpx_comm_wrap(void* nccl_comm, int world, int rank, int device, pcpx_comm**
     *out = nullptr;
     int st = need_rccl();
     if (st != PCPX_OK) return st;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) {
-        (void)hipGetLastError();
-        set_error("pcpx_comm_wrap: device %d is not available", device);
-        return PCPX_ERR_DEVICE;
-    }
-    DeviceGuard guard(device);
+    return on_device(device, "pcpx_comm_wrap", [&]() -> int {
     Comm* cm = nullptr;
     if ((st = make_comm(static_cast<ncclComm_t>(nccl_comm), false, world, rank, device, &cm)) != PCPX_OK) return st;
     *out = reinterpret_cast<pcpx_comm*>(cm);
     return PCPX_OK;
+    }, PCPX_ERR_DEVICE);  // (a communicator's device out of range is PCPX_ERR_DEVICE)
 }
 
 void pcpx_comm_destroy(pcpx_comm* h)
 {
     Comm* cm = reinterpret_cast<Comm*>(h);
     if (!cm) return;
-    DeviceGuard guard(cm->device);
+    DeviceScope scope;
+    (void)scope.use(cm->device);
     (void)hipDeviceSynchronize();
     if (cm->owned && cm->comm && rccl().ok) (void)rccl().CommDestroy(cm->comm);
     (void)hipFree(cm->d_work);
@@ -196,19 +175,16 @@ void pcpx_comm_destroy(pcpx_comm* h)
 
 int pcpx_comm_allgather_boxes_dev(pcpx_comm* h, const float* d_local6, float* d_all, void* stream)
 {
-    Comm* cm = reinterpret_cast<Comm*>(h);
-    if (!cm || !d_local6 || !d_all) return PCPX_ERR_INVALID;
-    DeviceGuard guard(cm->device);
-    std::lock_guard<std::mutex> lock(cm->mu);
+    return on_handle(reinterpret_cast<Comm*>(h), "pcpx_comm_allgather_boxes_dev", [&](Comm* cm) -> int {
+    if (!d_local6 || !d_all) return PCPX_ERR_INVALID;
     return check_nccl(rccl().AllGather(d_local6, d_all, 6, ncclFloat32, cm->comm, static_cast<hipStream_t>(stream)), "ncclAllGather");
+    });
 }
 
 int pcpx_comm_global_grid_dev(pcpx_comm* h, const float* d_xyz_slice, uint64_t n_slice, void* stream, float out_grid6[6])
 {
-    Comm* cm = reinterpret_cast<Comm*>(h);
-    if (!cm || !out_grid6 || (n_slice > 0 && !d_xyz_slice)) return PCPX_ERR_INVALID;
-    DeviceGuard guard(cm->device);
-    std::lock_guard<std::mutex> lock(cm->mu);
+    return on_handle(reinterpret_cast<Comm*>(h), "pcpx_comm_global_grid_dev", [&](Comm* cm) -> int {
+    if (!out_grid6 || (n_slice > 0 && !d_xyz_slice)) return PCPX_ERR_INVALID;
     hipStream_t s = static_cast<hipStream_t>(stream);
     float* d_local = cm->d_work + 8;   // decoded box of this rank's slice
     float* d_all = cm->d_work + 16;
@@ -222,6 +198,7 @@ int pcpx_comm_global_grid_dev(pcpx_comm* h, const float* d_xyz_slice, uint64_t n
     PCPX_HIP(hipMemcpyAsync(out_grid6, d_union, 6 * sizeof(float), hipMemcpyDeviceToHost, s));
     PCPX_HIP(hipStreamSynchronize(s));
     return PCPX_OK;
+    });
 }
 
 }  // extern "C"

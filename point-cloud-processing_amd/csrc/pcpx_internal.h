@@ -14,9 +14,9 @@
 #include <cstring>
 #include <hip/hip_runtime.h>
 
-#include <mutex>
-
 #include <cstdint>
+#include <mutex>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -474,6 +474,206 @@ struct HierarchyTimes {
 int hierarchy_device(const float* d_xyz, u64 n, u64 cluster_size, double var_max, hipStream_t s, DevPool& pool, float* d_out_xyz, u32* d_out_idx,
                      u64 capacity, u64* out_count, HierarchyTimes* times = nullptr);
 int launch_invert_perm(const u32* d_perm, u64 n, u32* d_position_of, hipStream_t s);
+
+// ---- the runtime (pcpx_runtime.hip) ---------------------------------------------------------------------------------------------
+extern thread_local std::string g_err;  // the thread's error text (pcpx_last_error)
+
+// RAII device buffer for the host-pointer entry points: a block of the owner's pool (no hipMalloc / hipFree per call);
+// returned to the pool on scope exit -- every such function synchronises its stream before it returns
+struct DevBuf {
+    void* p = nullptr;
+    DevPool* pool = nullptr;
+    bool one_off = false;  // true: not a block of the handle's pool (the n x 12-byte staging copy of a build from host memory
+                           // would stay cached for the handle's lifetime) but one of the device's index blocks: it serves the
+                           // next index built on this device, or goes back to the driver (index_block_alloc, pcpx_internal.h)
+    explicit DevBuf(DevPool& owner, bool one_off_ = false) : pool(&owner), one_off(one_off_) {}
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { reset(); }
+    void reset()
+    {
+        if (!p) return;
+        if (one_off) index_block_free(p);
+        else pool->release(p);
+        p = nullptr;
+    }
+    int alloc(size_t bytes)
+    {
+        if (one_off) {
+            const hipError_t e = index_block_alloc(&p, bytes);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                set_error("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+                p = nullptr;
+            }
+        } else {
+            p = pool->acquire(bytes);
+        }
+        return p ? PCPX_OK : PCPX_ERR_ALLOC;
+    }
+    template <class T>
+    T* as() const { return static_cast<T*>(p); }
+};
+
+// entry points without a handle (bounding box of a host array, one normal, the sort diagnostic) share one pool and one
+// pinned stage per device; they hold its mutex for their duration
+struct DeviceShared {
+    std::mutex mu;
+    DevPool pool;
+    PinnedStage pinned;
+    u32 normal_epoch = 0;  // launch counter of pcpx_estimate_normal's polled form
+};
+DeviceShared& shared_of(int device);
+
+// a stream of the per-device pool (pooled_stream_get) for the duration of a call; the caller synchronises it before it goes back
+struct PooledStream {
+    hipStream_t s = nullptr;
+    ~PooledStream() { pooled_stream_put(s); }
+};
+
+// Pageable host memory -> device on `stream`; the source may be reused when this returns (pcpx_runtime.hip)
+int upload_pageable(void* d_dst, const void* src, size_t bytes, hipStream_t stream);
+// PCPX_ERR_DEVICE without a device, `out_of_range` for a number that names none
+int select_device(int device, int out_of_range = PCPX_ERR_INVALID);
+// pcpx_build_params as this library knows it, from what the caller passed (ABI 3 and 4 callers pass less of it)
+int normalise_params(const pcpx_build_params* in, bool device_form, pcpx_build_params& out, const pcpx_build_params*& use);
+void free_index(Index* ix);  // drains the handle's stream, gives back its blocks and streams, deletes it
+// The latency paths: a kernel stores its launch number (the epoch) into a completion word in pinned memory when it is done, and
+// the host polls that word.  The counter's next value, never 0 (what a fresh word holds) ...
+inline u32 next_epoch(u32& counter) { return ++counter ? counter : ++counter; }
+// ... and the wait for it: polled, then (the kernel has not finished after the spin) on the stream
+int wait_epoch(const volatile u32* done, u32 epoch, hipStream_t s);
+
+// Every entry point makes its device current for its own duration only: the caller's thread gets its previous
+// current device back on return (a torch caller on cuda:1 must not find itself on cuda:0 after a pcpx call).
+struct DeviceScope {
+    int prev = -1;
+    void remember()
+    {
+        if (hipGetDevice(&prev) != hipSuccess) {
+            prev = -1;
+            (void)hipGetLastError();
+        }
+    }
+    int select(int device, int out_of_range = PCPX_ERR_INVALID)
+    {
+        remember();
+        int st = select_device(device, out_of_range);
+        if (prev == device) prev = -1;  // nothing to restore
+        return st;
+    }
+    int use(int device)  // (a handle's device: it existed when the handle was made)
+    {
+        remember();
+        if (prev == device) {
+            prev = -1;
+            return PCPX_OK;
+        }
+        PCPX_HIP(hipSetDevice(device));
+        return PCPX_OK;
+    }
+    ~DeviceScope()
+    {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+// Nothing may be thrown across the ABI: every prologue below runs its body through this
+template <class Body>
+int no_throw(const char* what, Body&& body)
+{
+    try {
+        return body();
+    } catch (const std::bad_alloc&) {
+        set_error("%s: out of host memory", what);
+        return PCPX_ERR_ALLOC;
+    } catch (...) {
+        set_error("%s: unexpected host exception", what);
+        return PCPX_ERR_INVALID;
+    }
+}
+
+// ---- the prologues of the extern "C" entry points ------------------------------------------------------------------------------
+// Each one restores the caller's current device on return, serialises calls on a handle, and lets nothing be thrown across the ABI
+// (a host exception becomes PCPX_ERR_ALLOC or PCPX_ERR_INVALID).  Checks that only look at the arguments may come before them.
+
+// entry points that use neither a device nor a handle (host arithmetic)
+template <class Body>
+int on_host(const char* what, Body&& body)
+{
+    return no_throw(what, body);
+}
+
+// entry points that take a handle with a `device` and a mutex `mu` (Index, the kd index, a communicator): the body gets the handle
+template <class Handle, class Body>
+int on_handle(Handle* h, const char* what, Body&& body)
+{
+    return no_throw(what, [&]() -> int {
+        if (!h) {
+            set_error("%s: null handle", what);
+            return PCPX_ERR_INVALID;
+        }
+        DeviceScope dscope;
+        int st = dscope.use(h->device);
+        if (st != PCPX_OK) return st;
+        std::lock_guard<decltype(h->mu)> serialise(h->mu);  // one call at a time per handle (queries share its scratch)
+        return body(h);
+    });
+}
+
+// entry points that take a pcpx_index*; flags WHOLE_CLOUD: a rank-local index is refused (shard_unsupported)
+constexpr int ANY_INDEX = 0, WHOLE_CLOUD = 1;
+template <class Body>
+int on_index(pcpx_index* h, const char* what, int flags, Body&& body)
+{
+    return on_handle(reinterpret_cast<Index*>(h), what, [&](Index* ix) -> int {
+        if ((flags & WHOLE_CLOUD) && ix->shard.on) return shard_unsupported(*ix, what);
+        return body(ix);
+    });
+}
+
+// entry points that take a device number: the body runs with that device current
+template <class Body>
+int on_device(int device, const char* what, Body&& body, int out_of_range = PCPX_ERR_INVALID)
+{
+    return no_throw(what, [&]() -> int {
+        DeviceScope dscope;
+        int st = dscope.select(device, out_of_range);
+        if (st != PCPX_OK) return st;
+        return body();
+    });
+}
+
+// ... and that also hold the device's DeviceShared (its pool and pinned stage): the body gets it
+template <class Body>
+int on_shared(int device, const char* what, Body&& body)
+{
+    return on_device(device, what, [&]() -> int {
+        DeviceShared& shared = shared_of(device);
+        std::lock_guard<std::mutex> lock(shared.mu);
+        return body(shared);
+    });
+}
+
+// ---- checks and views that several entry points share ------------------------------------------------------------------------
+// a slice of the curve order starts at a query group
+inline int check_slice(const char* what, u64 sorted_first)
+{
+    if (sorted_first % GROUP == 0) return PCPX_OK;
+    set_error("%s: sorted_first must be a multiple of %d", what, GROUP);
+    return PCPX_ERR_INVALID;
+}
+// the index's own points as queries
+inline QueryView self_view(const Index& ix) { return QueryView{nullptr, nullptr, nullptr, nullptr, nullptr, static_cast<u32>(ix.n)}; }
+// calls that need a neighbourhood for every input point
+inline int check_all_inserted(const Index& ix, const char* what)
+{
+    if (ix.n == ix.n_in) return PCPX_OK;
+    set_error("%s: %llu of %llu points lie outside the voxel grid and have no neighbourhood", what,
+              static_cast<unsigned long long>(ix.n_in - ix.n), static_cast<unsigned long long>(ix.n_in));
+    return PCPX_ERR_UNSUPPORTED;
+}
+
 int ensure_queue(Index& ix);   // the counters' allocation (zeroed)
 int sched_reserve(Index& ix, u64 groups);  // the arrays of the recorded order for launches of up to `groups` query groups (Index::sched)
 int prepare_queue(Index& ix);  // which set of work-queue counters the next persistent launch uses (Index::queue_now) and which it zeroes (queue_clear)

@@ -360,26 +360,6 @@ __global__ __launch_bounds__(SN_BLOCK) void k_sn_triangles(GridDev g, u32 nvert,
     }
 }
 
-// a block of the caller's pool, returned on scope exit
-struct PoolBuf {
-    DevPool& pool;
-    void* p = nullptr;
-    explicit PoolBuf(DevPool& owner) : pool(owner) {}
-    PoolBuf(const PoolBuf&) = delete;
-    PoolBuf& operator=(const PoolBuf&) = delete;
-    ~PoolBuf()
-    {
-        if (p) pool.release(p);
-    }
-    int alloc(size_t bytes)
-    {
-        p = pool.acquire(bytes > 0 ? bytes : 16);
-        return p ? PCPX_OK : PCPX_ERR_ALLOC;
-    }
-    template <class T>
-    T* as() const { return static_cast<T*>(p); }
-};
-
 int grid_to_dev(const pcpx_grid3d& g, GridDev& d, u64& ncubes)
 {
     ncubes = 0;
@@ -431,7 +411,7 @@ int surface_nets_device(const float* d_field, const pcpx_grid3d& grid, float iso
         }
     } events_gone{ev};
     // pass 1: flags, scanned in place into vertex offsets (ncubes + 1 entries)
-    PoolBuf vofs(pool), sums(pool), map(pool);
+    DevBuf vofs(pool), sums(pool), map(pool);
     const u64 tiles_c = (ncubes + 1 + SCAN_TILE - 1) / SCAN_TILE;
     if ((st = vofs.alloc((ncubes + 1) * sizeof(u32))) != PCPX_OK || (st = map.alloc(ncubes * sizeof(u32))) != PCPX_OK ||
         (st = sums.alloc(std::max<u64>(tiles_c, 64) * sizeof(u64))) != PCPX_OK)
@@ -448,7 +428,7 @@ int surface_nets_device(const float* d_field, const pcpx_grid3d& grid, float iso
     const u64 nv = nv32;
     *out_nv = nv;
     // pass 2: the map, the active cubes, and the vertices if they fit
-    PoolBuf active(pool), tofs(pool), tsums(pool);
+    DevBuf active(pool), tofs(pool), tsums(pool);
     const u64 tiles_v = (nv + 1 + SCAN_TILE - 1) / SCAN_TILE;
     if ((st = active.alloc(nv * sizeof(u32))) != PCPX_OK || (st = tofs.alloc((nv + 1) * sizeof(u64))) != PCPX_OK ||
         (st = tsums.alloc(std::max<u64>(tiles_v, 64) * sizeof(u64))) != PCPX_OK)
@@ -511,7 +491,7 @@ int tangent_plane_sdf_device(Index& ix, const float* d_centroids, const float* d
         return PCPX_ERR_INVALID;
     }
     hipStream_t s = ix.stream;
-    PoolBuf q(ix.pool), nn(ix.pool), cnt(ix.pool);
+    DevBuf q(ix.pool), nn(ix.pool), cnt(ix.pool);
     if ((st = q.alloc(nq * 3 * sizeof(float))) != PCPX_OK || (st = nn.alloc(nq * sizeof(u32))) != PCPX_OK ||
         (st = cnt.alloc(nq * sizeof(u32))) != PCPX_OK)
         return st;
@@ -530,3 +510,162 @@ int tangent_plane_sdf_device(Index& ix, const float* d_centroids, const float* d
 }
 
 }  // namespace pcpx
+
+using namespace pcpx;
+
+extern "C" {
+
+// ---- surface reconstruction (pcpx_isosurface.hip) -------------------------------------------------------------------------
+
+int pcpx_regular_grid_containing(const float min3[3], const float max3[3], const uint64_t dims[3], pcpx_grid3d* out)
+{
+    if (!min3 || !max3 || !dims || !out) return PCPX_ERR_INVALID;
+    pcpx_grid3d g{};
+    g.x = min3[0], g.y = min3[1], g.z = min3[2];
+    g.sx = dims[0], g.sy = dims[1], g.sz = dims[2];
+    g.dx = (max3[0] - min3[0]) / static_cast<float>(g.sx);
+    g.dy = (max3[1] - min3[1]) / static_cast<float>(g.sy);
+    g.dz = (max3[2] - min3[2]) / static_cast<float>(g.sz);
+    g.x -= g.dx;
+    g.y -= g.dx;  // (sic: regular_grid3d.hpp:84-86 moves every axis back by dx)
+    g.z -= g.dx;
+    g.sx += 2, g.sy += 2, g.sz += 2;
+    *out = g;
+    return PCPX_OK;
+}
+
+int pcpx_surface_nets_timed_dev(const float* d_field, const pcpx_grid3d* grid, float isovalue, int device, void* stream, float* d_out_xyz,
+                                uint64_t vertex_capacity, uint32_t* d_out_tri, uint64_t triangle_capacity, uint64_t* out_nvertices,
+                                uint64_t* out_ntriangles, float out_pass_ms[3])
+{
+    if (!grid || !out_nvertices || !out_ntriangles) return PCPX_ERR_INVALID;
+    *out_nvertices = *out_ntriangles = 0;
+    return on_shared(device, "pcpx_surface_nets_dev", [&](DeviceShared& sh) -> int {
+        SurfaceNetsTimes t;
+        const int r = surface_nets_device(d_field, *grid, isovalue, static_cast<hipStream_t>(stream), sh.pool, d_out_xyz, vertex_capacity,
+                                          d_out_tri, triangle_capacity, out_nvertices, out_ntriangles, out_pass_ms ? &t : nullptr);
+        if (out_pass_ms) out_pass_ms[0] = t.flags_ms, out_pass_ms[1] = t.vertices_ms, out_pass_ms[2] = t.triangles_ms;
+        return r;
+    });
+}
+
+int pcpx_surface_nets_dev(const float* d_field, const pcpx_grid3d* grid, float isovalue, int device, void* stream, float* d_out_xyz,
+                          uint64_t vertex_capacity, uint32_t* d_out_tri, uint64_t triangle_capacity, uint64_t* out_nvertices,
+                          uint64_t* out_ntriangles)
+{
+    return pcpx_surface_nets_timed_dev(d_field, grid, isovalue, device, stream, d_out_xyz, vertex_capacity, d_out_tri, triangle_capacity,
+                                       out_nvertices, out_ntriangles, nullptr);
+}
+
+int pcpx_surface_nets(const float* field, const pcpx_grid3d* grid, float isovalue, int device, float* out_xyz, uint64_t vertex_capacity,
+                      uint32_t* out_tri, uint64_t triangle_capacity, uint64_t* out_nvertices, uint64_t* out_ntriangles)
+{
+    if (!grid || !out_nvertices || !out_ntriangles) return PCPX_ERR_INVALID;
+    *out_nvertices = *out_ntriangles = 0;
+    if (grid->sx == 0 || grid->sy == 0 || grid->sz == 0) return PCPX_OK;
+    if (!field) return PCPX_ERR_INVALID;
+    const int valid = check_surface_grid(*grid);  // (before the field is read)
+    if (valid != PCPX_OK) return valid;
+    return on_shared(device, "pcpx_surface_nets", [&](DeviceShared& sh) -> int {
+        PooledStream ps;
+        PCPX_HIP(pooled_stream_get(&ps.s));
+        const hipStream_t s = ps.s;
+        const u64 corners = (grid->sx + 1) * (grid->sy + 1) * (grid->sz + 1);
+        DevBuf df(sh.pool), dv(sh.pool), dt(sh.pool);
+        int r;
+        if ((r = df.alloc(corners * sizeof(float))) != PCPX_OK) return r;
+        const u64 vcap = out_xyz ? vertex_capacity : 0, tcap = out_tri ? triangle_capacity : 0;
+        if ((vcap > 0 && (r = dv.alloc(vcap * 3 * sizeof(float))) != PCPX_OK) || (tcap > 0 && (r = dt.alloc(tcap * 3 * sizeof(u32))) != PCPX_OK))
+            return r;
+        if ((r = upload_pageable(df.p, field, corners * sizeof(float), s)) != PCPX_OK) return r;
+        r = surface_nets_device(df.as<float>(), *grid, isovalue, s, sh.pool, dv.as<float>(), vcap, dt.as<u32>(), tcap, out_nvertices,
+                                out_ntriangles);
+        if (r != PCPX_OK) return r;
+        if (*out_nvertices) PCPX_HIP(hipMemcpyAsync(out_xyz, dv.p, *out_nvertices * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (*out_ntriangles) PCPX_HIP(hipMemcpyAsync(out_tri, dt.p, *out_ntriangles * 3 * sizeof(u32), hipMemcpyDeviceToHost, s));
+        PCPX_HIP(hipStreamSynchronize(s));
+        return PCPX_OK;
+    });
+}
+
+int pcpx_tangent_plane_sdf_dev(pcpx_index* h, const float* d_centroids, const float* d_normals, const pcpx_grid3d* grid, float eps,
+                               float* d_out_field)
+{
+    return on_index(h, "pcpx_tangent_plane_sdf_dev", WHOLE_CLOUD, [&](Index* ix) -> int {
+    if (!grid || !d_centroids || !d_normals || !d_out_field) return PCPX_ERR_INVALID;
+    return tangent_plane_sdf_device(*ix, d_centroids, d_normals, *grid, eps, d_out_field);
+    });
+}
+
+// the pipeline of examples/tangent_plane_surface_reconstruction.cpp:233-455 after the tree, device resident
+static int reconstruct_device(Index* ix, u32 k, float eps, const uint64_t dims[3], float iso, float* d_xyz, u64 vcap, u32* d_tri, u64 tcap,
+                              u64* out_nv, u64* out_nt, float* d_opt_centroids, float* d_opt_normals, pcpx_grid3d* opt_grid)
+{
+    pcpx_index* h = reinterpret_cast<pcpx_index*>(ix);
+    if (k == 0 || !dims || !out_nv || !out_nt) return PCPX_ERR_INVALID;
+    *out_nv = *out_nt = 0;
+    int st = check_all_inserted(*ix, "pcpx_reconstruct_surface");
+    if (st != PCPX_OK) return st;
+    const u64 rows = ix->n_in;
+    if (rows == 0) return PCPX_OK;
+    DevBuf dc(ix->pool), dn(ix->pool), di(ix->pool), dk(ix->pool), df(ix->pool);
+    float* d_c = d_opt_centroids;
+    float* d_n = d_opt_normals;
+    if ((!d_c && (st = dc.alloc(rows * 3 * sizeof(float))) != PCPX_OK) || (!d_n && (st = dn.alloc(rows * 3 * sizeof(float))) != PCPX_OK) ||
+        (st = di.alloc(rows * k * sizeof(u32))) != PCPX_OK || (st = dk.alloc(rows * sizeof(u32))) != PCPX_OK)
+        return st;
+    if (!d_c) d_c = dc.as<float>();
+    if (!d_n) d_n = dn.as<float>();
+    // 1-2: tangent planes (estimate_tangent_planes), then propagate_normal_orientations over the kNN rows
+    if ((st = pcpx_neighbourhoods_self_dev(h, k, eps, 0, UINT64_MAX, d_n, d_c, nullptr)) != PCPX_OK) return st;
+    if ((st = pcpx_knn_self_dev(h, k, eps, 0, UINT64_MAX, di.as<u32>(), dk.as<u32>(), nullptr)) != PCPX_OK) return st;
+    if ((st = orient_normals_device(ix->d_xyz, rows, di.as<u32>(), dk.as<u32>(), k, d_n, ix->stream, nullptr, nullptr)) != PCPX_OK) return st;
+    // 3: the grid around the index's box
+    pcpx_grid3d g{};
+    if ((st = pcpx_regular_grid_containing(ix->bbox, ix->bbox + 3, dims, &g)) != PCPX_OK) return st;
+    if (opt_grid) *opt_grid = g;
+    // 4-5: the field, surface nets
+    const u64 corners = (g.sx + 1) * (g.sy + 1) * (g.sz + 1);
+    if ((st = df.alloc(corners * sizeof(float))) != PCPX_OK) return st;
+    if ((st = tangent_plane_sdf_device(*ix, d_c, d_n, g, eps, df.as<float>())) != PCPX_OK) return st;
+    return surface_nets_device(df.as<float>(), g, iso, ix->stream, ix->pool, d_xyz, vcap, d_tri, tcap, out_nv, out_nt);
+}
+
+int pcpx_reconstruct_surface_dev(pcpx_index* h, uint32_t k, float eps, const uint64_t dims[3], float isovalue, float* d_out_xyz,
+                                 uint64_t vertex_capacity, uint32_t* d_out_tri, uint64_t triangle_capacity, uint64_t* out_nvertices,
+                                 uint64_t* out_ntriangles, float* d_opt_out_centroids, float* d_opt_out_normals, pcpx_grid3d* opt_out_grid)
+{
+    return on_index(h, "pcpx_reconstruct_surface_dev", WHOLE_CLOUD, [&](Index* ix) {
+        return reconstruct_device(ix, k, eps, dims, isovalue, d_out_xyz, vertex_capacity, d_out_tri, triangle_capacity, out_nvertices,
+                                  out_ntriangles, d_opt_out_centroids, d_opt_out_normals, opt_out_grid);
+    });
+}
+
+int pcpx_reconstruct_surface(pcpx_index* h, uint32_t k, float eps, const uint64_t dims[3], float isovalue, float* out_xyz,
+                             uint64_t vertex_capacity, uint32_t* out_tri, uint64_t triangle_capacity, uint64_t* out_nvertices,
+                             uint64_t* out_ntriangles, float* opt_out_centroids, float* opt_out_normals, pcpx_grid3d* opt_out_grid)
+{
+    return on_index(h, "pcpx_reconstruct_surface", WHOLE_CLOUD, [&](Index* ix) -> int {
+        const u64 rows = ix->n_in;
+        const u64 vcap = out_xyz ? vertex_capacity : 0, tcap = out_tri ? triangle_capacity : 0;
+        DevBuf dv(ix->pool), dt(ix->pool), dc(ix->pool), dn(ix->pool);
+        int r;
+        if ((vcap > 0 && (r = dv.alloc(vcap * 3 * sizeof(float))) != PCPX_OK) || (tcap > 0 && (r = dt.alloc(tcap * 3 * sizeof(u32))) != PCPX_OK) ||
+            (opt_out_centroids && rows > 0 && (r = dc.alloc(rows * 3 * sizeof(float))) != PCPX_OK) ||
+            (opt_out_normals && rows > 0 && (r = dn.alloc(rows * 3 * sizeof(float))) != PCPX_OK))
+            return r;
+        r = reconstruct_device(ix, k, eps, dims, isovalue, dv.as<float>(), vcap, dt.as<u32>(), tcap, out_nvertices, out_ntriangles,
+                               dc.as<float>(), dn.as<float>(), opt_out_grid);
+        if (r != PCPX_OK && r != PCPX_ERR_CAPACITY) return r;
+        if (r == PCPX_OK) {
+            if (*out_nvertices) PCPX_HIP(hipMemcpyAsync(out_xyz, dv.p, *out_nvertices * 3 * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+            if (*out_ntriangles) PCPX_HIP(hipMemcpyAsync(out_tri, dt.p, *out_ntriangles * 3 * sizeof(u32), hipMemcpyDeviceToHost, ix->stream));
+        }
+        if (dc.p) PCPX_HIP(hipMemcpyAsync(opt_out_centroids, dc.p, rows * 3 * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+        if (dn.p) PCPX_HIP(hipMemcpyAsync(opt_out_normals, dn.p, rows * 3 * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+        PCPX_HIP(hipStreamSynchronize(ix->stream));
+        return r;
+    });
+}
+
+}  // extern "C"

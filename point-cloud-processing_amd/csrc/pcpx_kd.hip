@@ -34,35 +34,6 @@ struct KdIndex {
     std::mutex mu;
 };
 
-template <class Body>
-int kd_no_throw(const char* what, Body&& body)
-{
-    try {
-        return body();
-    } catch (const std::bad_alloc&) {
-        set_error("%s: out of host memory", what);
-        return PCPX_ERR_ALLOC;
-    } catch (...) {
-        set_error("%s: unexpected host exception", what);
-        return PCPX_ERR_INVALID;
-    }
-}
-
-struct KdDeviceScope {
-    int before = -1;
-    int use(int device)
-    {
-        PCPX_HIP(hipGetDevice(&before));
-        if (before != device) PCPX_HIP(hipSetDevice(device));
-        else before = -1;
-        return PCPX_OK;
-    }
-    ~KdDeviceScope()
-    {
-        if (before >= 0) (void)hipSetDevice(before);
-    }
-};
-
 struct KdBuf {
     void* p = nullptr;
     int alloc(size_t bytes)
@@ -224,26 +195,14 @@ extern "C" {
 
 int pcpx_kd_create(const float* points, uint64_t n, uint32_t dims, int device, pcpx_kd_index** out)
 {
-    return kd_no_throw("pcpx_kd_create", [&]() -> int {
-        if (!out) return PCPX_ERR_INVALID;
-        *out = nullptr;
-        if (dims < 1 || dims > KD_MAX_DIMS || (n > 0 && !points) || n >= 0xFFFFFFFFull) {
-            set_error("pcpx_kd_create: 1 <= dims <= %u, fewer than 2^32 - 1 points", KD_MAX_DIMS);
-            return PCPX_ERR_INVALID;
-        }
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || count == 0) {
-            (void)hipGetLastError();
-            set_error("pcpx: no HIP device available; libpcpx has no CPU fallback");
-            return PCPX_ERR_DEVICE;
-        }
-        if (device < 0 || device >= count) {
-            set_error("pcpx: device %d out of range [0,%d)", device, count);
-            return PCPX_ERR_INVALID;
-        }
-        KdDeviceScope scope;
-        int st = scope.use(device);
-        if (st != PCPX_OK) return st;
+    if (!out) return PCPX_ERR_INVALID;
+    *out = nullptr;
+    if (dims < 1 || dims > KD_MAX_DIMS || (n > 0 && !points) || n >= 0xFFFFFFFFull) {
+        set_error("pcpx_kd_create: 1 <= dims <= %u, fewer than 2^32 - 1 points", KD_MAX_DIMS);
+        return PCPX_ERR_INVALID;
+    }
+    return on_device(device, "pcpx_kd_create", [&]() -> int {
+        int st;
         KdIndex* ix = new KdIndex;
         ix->device = device;
         ix->n = n;
@@ -275,7 +234,7 @@ void pcpx_kd_destroy(pcpx_kd_index* h)
 {
     KdIndex* ix = reinterpret_cast<KdIndex*>(h);
     if (!ix) return;
-    KdDeviceScope scope;
+    DeviceScope scope;
     (void)scope.use(ix->device);
     if (ix->stream) (void)hipStreamSynchronize(ix->stream);
     if (ix->d_pts) (void)hipFree(ix->d_pts);
@@ -289,12 +248,7 @@ uint32_t pcpx_kd_dims(const pcpx_kd_index* h) { return h ? reinterpret_cast<cons
 int pcpx_kd_knn_batch(pcpx_kd_index* h, const float* queries, uint64_t nq, uint32_t k, float eps, uint32_t* out_idx, uint32_t* out_count,
                       float* opt_out_d2)
 {
-    return kd_no_throw("pcpx_kd_knn_batch", [&]() -> int {
-        KdIndex* ix = reinterpret_cast<KdIndex*>(h);
-        if (!ix) {
-            set_error("pcpx: null index handle");
-            return PCPX_ERR_INVALID;
-        }
+    return on_handle(reinterpret_cast<KdIndex*>(h), "pcpx_kd_knn_batch", [&](KdIndex* ix) -> int {
         if (nq > 0 && (!queries || !out_count || (k > 0 && !out_idx))) return PCPX_ERR_INVALID;
         if (nq == 0) return PCPX_OK;
         if (k == 0 || ix->n == 0) {
@@ -305,10 +259,7 @@ int pcpx_kd_knn_batch(pcpx_kd_index* h, const float* queries, uint64_t nq, uint3
             }
             return PCPX_OK;
         }
-        KdDeviceScope scope;
-        int st = scope.use(ix->device);
-        if (st != PCPX_OK) return st;
-        std::lock_guard<std::mutex> serialise(ix->mu);
+        int st;
         if (!(eps > 0.f)) eps = 0.f;  // eps <= 0 or NaN: nothing is "equal"
         u32 nseg = 1, seg_points = 64;
         kd_segments(ix->n, nq, nseg, seg_points);
@@ -344,12 +295,7 @@ int pcpx_kd_knn_batch(pcpx_kd_index* h, const float* queries, uint64_t nq, uint3
 
 int pcpx_kd_range_aabb_batch(pcpx_kd_index* h, const float* boxes, uint64_t nb, uint64_t* out_offsets, uint32_t* out_idx, uint64_t idx_capacity)
 {
-    return kd_no_throw("pcpx_kd_range_aabb_batch", [&]() -> int {
-        KdIndex* ix = reinterpret_cast<KdIndex*>(h);
-        if (!ix) {
-            set_error("pcpx: null index handle");
-            return PCPX_ERR_INVALID;
-        }
+    return on_handle(reinterpret_cast<KdIndex*>(h), "pcpx_kd_range_aabb_batch", [&](KdIndex* ix) -> int {
         if (!out_offsets || (nb > 0 && !boxes)) return PCPX_ERR_INVALID;
         out_offsets[0] = 0;
         if (nb == 0) return PCPX_OK;
@@ -357,10 +303,7 @@ int pcpx_kd_range_aabb_batch(pcpx_kd_index* h, const float* boxes, uint64_t nb, 
             for (u64 i = 0; i <= nb; ++i) out_offsets[i] = 0;
             return PCPX_OK;
         }
-        KdDeviceScope scope;
-        int st = scope.use(ix->device);
-        if (st != PCPX_OK) return st;
-        std::lock_guard<std::mutex> serialise(ix->mu);
+        int st;
         u32 nseg = 1, seg_points = 64;
         kd_segments(ix->n, nb, nseg, seg_points);
         if (nb * nseg > 0x7FFFFFFFull) {

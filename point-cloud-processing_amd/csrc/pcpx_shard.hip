@@ -841,3 +841,76 @@ int shard_perm(Index& ix, u32* d_out_perm, u32* d_out_pos)
 }
 
 }  // namespace pcpx
+
+using namespace pcpx;
+
+// cost of a sampled group from its event counts, in instructions of the k <= 16 kernel (ISA counts, DESIGN.md "k_knn budget"): an
+// expansion is 4 box tests + the walk's scalar side, a dense leaf 8 candidates x 64 lanes, a packed leaf its publish + read-back and
+// ~10 per step of eight needing lanes, a fold the selection network; the constant is a group's seed phase, cap and epilogue.
+static inline uint64_t group_cost_of(const uint32_t e[4])
+{
+    const uint64_t folds = e[3] >> 16, steps = e[3] & 0xFFFFu, dense = e[1] & 0xFFFFFFu, packed = e[2] & 0xFFFFFu;
+    return 6000ull + 112ull * e[0] + 108ull * dense + 38ull * packed + 11ull * steps + 140ull * folds;
+}
+
+extern "C" {
+
+int pcpx_shard_cuts_by_cost(uint64_t n, uint32_t world, uint32_t group_stride, const uint32_t* events, uint64_t nsamples, uint64_t* out_first)
+{
+    if (!out_first || world == 0 || group_stride == 0 || (nsamples && !events)) return PCPX_ERR_INVALID;
+    return on_host("pcpx_shard_cuts_by_cost", [&]() -> int {
+    const u64 groups = (n + GROUP - 1) / GROUP;
+    if (nsamples != groups / group_stride) {
+        set_error("pcpx_shard_cuts_by_cost: %llu samples do not describe %llu groups at stride %u", static_cast<unsigned long long>(nsamples),
+                  static_cast<unsigned long long>(groups), group_stride);
+        return PCPX_ERR_INVALID;
+    }
+    out_first[0] = 0;
+    out_first[world] = n;
+    if (nsamples == 0) {  // too small to sample: cut by count
+        for (u32 r = 1; r < world; ++r) {
+            u64 f = groups * r / world * GROUP;
+            out_first[r] = f > n ? n : f;
+        }
+        return PCPX_OK;
+    }
+    // cost per group, block by block (sample i stands for groups [i stride, (i + 1) stride); the tail beyond the last whole block takes
+    // the last sample's), prefix sums in 64-bit integers: every rank of a job gets the same cuts from the same counts
+    std::vector<u64> prefix(nsamples + 2, 0);
+    for (u64 i = 0; i < nsamples; ++i) prefix[i + 1] = prefix[i] + group_cost_of(events + 4 * i) * group_stride;
+    const u64 tail_groups = groups - nsamples * group_stride;
+    prefix[nsamples + 1] = prefix[nsamples] + group_cost_of(events + 4 * (nsamples - 1)) * tail_groups;
+    const u64 total = prefix[nsamples + 1];
+    u64 i = 0;
+    for (u32 r = 1; r < world; ++r) {
+        const u64 target = static_cast<u64>((static_cast<unsigned __int128>(total) * r) / world);
+        while (i + 1 < nsamples + 1 && prefix[i + 1] <= target) ++i;  // block i holds the target
+        const u64 block_groups = i < nsamples ? group_stride : tail_groups;
+        const u64 block_cost = prefix[i + 1] - prefix[i];
+        u64 inside = block_cost ? static_cast<u64>((static_cast<unsigned __int128>(target - prefix[i]) * block_groups) / block_cost) : 0;
+        if (inside > block_groups) inside = block_groups;
+        u64 g = i * group_stride + inside;
+        if (g > groups) g = groups;
+        u64 f = g * GROUP;
+        if (f > n) f = n;
+        if (f < out_first[r - 1]) f = out_first[r - 1];
+        out_first[r] = f;
+    }
+    return PCPX_OK;
+    });
+}
+
+int pcpx_shard_range(uint64_t n, uint32_t rank, uint32_t world, uint64_t* out_first, uint64_t* out_count)
+{
+    if (!out_first || !out_count || world == 0 || rank >= world) return PCPX_ERR_INVALID;
+    u64 groups = (n + GROUP - 1) / GROUP;
+    u64 g0 = groups * rank / world, g1 = groups * (static_cast<u64>(rank) + 1) / world;
+    u64 first = g0 * GROUP, end = g1 * GROUP;
+    if (first > n) first = n;
+    if (end > n) end = n;
+    *out_first = first;
+    *out_count = end - first;
+    return PCPX_OK;
+}
+
+}  // extern "C"

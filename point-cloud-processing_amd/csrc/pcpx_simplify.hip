@@ -546,25 +546,6 @@ u32 wave_blocks(u64 waves)
 }
 u32 thread_blocks(u64 threads) { return static_cast<u32>((threads + HS_BLOCK - 1) / HS_BLOCK); }
 
-struct PoolBuf {
-    DevPool& pool;
-    void* p = nullptr;
-    explicit PoolBuf(DevPool& owner) : pool(owner) {}
-    PoolBuf(const PoolBuf&) = delete;
-    PoolBuf& operator=(const PoolBuf&) = delete;
-    ~PoolBuf()
-    {
-        if (p) pool.release(p);
-    }
-    int alloc(size_t bytes)
-    {
-        p = pool.acquire(bytes > 0 ? bytes : 16);
-        return p ? PCPX_OK : PCPX_ERR_ALLOC;
-    }
-    template <class T>
-    T* as() const { return static_cast<T*>(p); }
-};
-
 }  // namespace
 
 int hierarchy_device(const float* d_xyz, u64 n, u64 cluster_size, double var_max, hipStream_t s, DevPool& pool, float* d_out_xyz, u32* d_out_idx,
@@ -588,7 +569,7 @@ int hierarchy_device(const float* d_xyz, u64 n, u64 cluster_size, double var_max
     const u32 n32 = static_cast<u32>(n);
     const u64 max_chunks = n + (n + HS_CHUNK - 1) / HS_CHUNK;  // sum over clusters of ceil(L / CHUNK) <= n / CHUNK + clusters
     const u64 scan_tiles = (n + 1 + HS_SCAN_TILE - 1) / HS_SCAN_TILE;
-    PoolBuf rec0(pool), rec1(pool), cl0(pool), cl1(pool), ch00(pool), ch01(pool), stb(pool), pkb(pool), sums(pool), part(pool), cnt(pool),
+    DevBuf rec0(pool), rec1(pool), cl0(pool), cl1(pool), ch00(pool), ch01(pool), stb(pool), pkb(pool), sums(pool), part(pool), cnt(pool),
         bd2(pool), bidx(pool), outi(pool), ctlb(pool);
     int st;
     if ((st = rec0.alloc(n * sizeof(float4))) != PCPX_OK || (st = rec1.alloc(n * sizeof(float4))) != PCPX_OK ||
@@ -685,3 +666,75 @@ int hierarchy_device(const float* d_xyz, u64 n, u64 cluster_size, double var_max
 }
 
 }  // namespace pcpx
+
+using namespace pcpx;
+
+static int hierarchy_params_of(const pcpx_hierarchy_params* params, u64& cluster_size, double& var_max)
+{
+    if (!params || params->struct_size != sizeof(pcpx_hierarchy_params)) {
+        set_error("pcpx_hierarchy_simplification: params missing or params->struct_size mismatch");
+        return PCPX_ERR_INVALID;
+    }
+    cluster_size = params->cluster_size;
+    var_max = params->var_max;
+    if (cluster_size == 0 || !(var_max >= 0.0)) {
+        set_error("pcpx_hierarchy_simplification: cluster_size must be > 0 and var_max >= 0 (not NaN)");
+        return PCPX_ERR_INVALID;
+    }
+    return PCPX_OK;
+}
+
+extern "C" {
+
+int pcpx_hierarchy_simplification_dev(const float* d_xyz, uint64_t n, const pcpx_hierarchy_params* params, int device, void* stream,
+                                      float* d_out_xyz, uint32_t* d_opt_out_idx, uint64_t capacity, uint64_t* out_count)
+{
+    if (!out_count) return PCPX_ERR_INVALID;
+    *out_count = 0;
+    u64 cluster_size = 0;
+    double var_max = 0;
+    int st = hierarchy_params_of(params, cluster_size, var_max);
+    if (st != PCPX_OK) return st;
+    return on_shared(device, "pcpx_hierarchy_simplification_dev", [&](DeviceShared& sh) -> int {
+        return hierarchy_device(d_xyz, n, cluster_size, var_max, static_cast<hipStream_t>(stream), sh.pool, d_out_xyz, d_opt_out_idx, capacity,
+                                out_count);
+    });
+}
+
+int pcpx_hierarchy_simplification(const float* xyz, uint64_t n, const pcpx_hierarchy_params* params, int device, float* out_xyz,
+                                  uint32_t* opt_out_idx, uint64_t capacity, uint64_t* out_count)
+{
+    if (!out_count) return PCPX_ERR_INVALID;
+    *out_count = 0;
+    u64 cluster_size = 0;
+    double var_max = 0;
+    int st = hierarchy_params_of(params, cluster_size, var_max);
+    if (st != PCPX_OK) return st;
+    if (n == 0) return PCPX_OK;
+    if (!xyz || n >= 0xFFFFFFFFull) {
+        set_error("pcpx_hierarchy_simplification: null points or more than 2^32 - 2 of them");
+        return PCPX_ERR_INVALID;
+    }
+    return on_shared(device, "pcpx_hierarchy_simplification", [&](DeviceShared& sh) -> int {
+        PooledStream ps;
+        PCPX_HIP(pooled_stream_get(&ps.s));
+        const hipStream_t s = ps.s;
+        const u64 cap = out_xyz ? std::min<u64>(capacity, n) : 0;
+        DevBuf dp(sh.pool), dv(sh.pool), di(sh.pool);
+        int r;
+        if ((r = dp.alloc(n * 3 * sizeof(float))) != PCPX_OK || (cap > 0 && (r = dv.alloc(cap * 3 * sizeof(float))) != PCPX_OK) ||
+            (cap > 0 && opt_out_idx && (r = di.alloc(cap * sizeof(u32))) != PCPX_OK))
+            return r;
+        if ((r = upload_pageable(dp.p, xyz, n * 3 * sizeof(float), s)) != PCPX_OK) return r;
+        r = hierarchy_device(dp.as<float>(), n, cluster_size, var_max, s, sh.pool, cap > 0 ? dv.as<float>() : nullptr, di.as<u32>(), cap, out_count);
+        if (r != PCPX_OK) return r;
+        if (*out_count) {
+            PCPX_HIP(hipMemcpyAsync(out_xyz, dv.p, *out_count * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+            if (opt_out_idx) PCPX_HIP(hipMemcpyAsync(opt_out_idx, di.p, *out_count * sizeof(u32), hipMemcpyDeviceToHost, s));
+        }
+        PCPX_HIP(hipStreamSynchronize(s));
+        return PCPX_OK;
+    });
+}
+
+}  // extern "C"

@@ -202,8 +202,8 @@ def test_gpu_normals_on_analytic_cases(pkg, oracle):
 
 
 def test_host_calls_equal_the_device_resident_path(pkg):
-    """Host-pointer self queries stage through the handle's pooled device buffers (pcpx_api.hip, self_queries_to_host);
-    the rows, counts, distances and normals must be the ones the *_dev forms write into the caller's device memory --
+    """Host-pointer self queries stage through the handle's pooled device buffers (self_queries_to_host in csrc/pcpx_api.hip,
+    DevPool in csrc/pcpx_runtime.hip); the rows, counts, distances and normals must be the ones the *_dev forms write into the caller's device memory --
     bit for bit -- and stay so after the pool has been trimmed."""
     torch = pytest.importorskip("torch")
     n, k = 2_600_000, 15
