@@ -479,6 +479,39 @@ int pcpx_surface_nets_timed_dev(const float* d_field, const pcpx_grid3d* grid, f
 /* Host arrays. */
 int pcpx_surface_nets(const float* field, const pcpx_grid3d* grid, float isovalue, int device, float* out_xyz, uint64_t vertex_capacity,
                       uint32_t* out_tri, uint64_t triangle_capacity, uint64_t* out_nvertices, uint64_t* out_ntriangles);
+/* Surface nets seeded by a hint point (surface_nets.hpp:653-1119, the overload with a hint): only the connected component of
+ * the isosurface that the reference's search from the hint reaches first.  Contract:
+ *  - the hint cube is floor((hint - origin) / voxel size) per axis, in float (the reference's truncation for values >= 0);
+ *    it may lie outside the grid.  A non-finite hint, or a NaN grid coordinate, is PCPX_ERR_INVALID;
+ *  - the seed is the first active grid cube in the reference's first-pop order around the hint cube, a fixed table of offsets
+ *    (pcpx_surface_nets_search_order).  Where that order's queue reaches exactly queue_max cubes, the table ends there and a
+ *    table with no active cube gives the whole-grid mesh, byte-identical to pcpx_surface_nets_dev (*opt_out_seed_cube =
+ *    UINT64_MAX).  Where it never does within 2^20 pops (queue_max 0: never), the search is unbounded: with no table entry
+ *    active, the seed is the active cube nearest the hint cube in Manhattan distance, the smallest cube index on a tie;
+ *  - two active cubes are connected iff they share a bipolar edge; cubes outside the grid are never active (the reference
+ *    walks linear indices across faces and evaluates f outside the grid);
+ *  - the result is exactly the whole-grid mesh restricted to the seed's component: its vertices, bit for bit, in ascending
+ *    cube index, and the whole-grid triangles whose four cubes are all in the component, indices remapped (the reference's
+ *    order is its search order).
+ * Outputs, the capacity protocol and the grid limits as pcpx_surface_nets_dev; *opt_out_seed_cube (may be NULL) receives the
+ * seed's linear cube index i + j*sx + k*sx*sy, or UINT64_MAX (whole grid, or no active cube).  Synchronises `stream`. */
+int pcpx_surface_nets_hint_dev(const float* d_field, const pcpx_grid3d* grid, float isovalue, const float hint[3], uint64_t queue_max, int device,
+                               void* stream, float* d_out_xyz, uint64_t vertex_capacity, uint32_t* d_out_tri, uint64_t triangle_capacity,
+                               uint64_t* out_nvertices, uint64_t* out_ntriangles, uint64_t* opt_out_seed_cube);
+/* The same with device-event times of its five phases in ms (active cubes; seed; component labelling; restriction and
+ * vertices; triangles) and, in *opt_out_rounds (may be NULL), the hook launches of the labelling (1; 0 without a seed). */
+int pcpx_surface_nets_hint_timed_dev(const float* d_field, const pcpx_grid3d* grid, float isovalue, const float hint[3], uint64_t queue_max,
+                                     int device, void* stream, float* d_out_xyz, uint64_t vertex_capacity, uint32_t* d_out_tri,
+                                     uint64_t triangle_capacity, uint64_t* out_nvertices, uint64_t* out_ntriangles, uint64_t* opt_out_seed_cube,
+                                     float out_phase_ms[5], uint32_t* opt_out_rounds);
+/* Host arrays. */
+int pcpx_surface_nets_hint(const float* field, const pcpx_grid3d* grid, float isovalue, const float hint[3], uint64_t queue_max, int device,
+                           float* out_xyz, uint64_t vertex_capacity, uint32_t* out_tri, uint64_t triangle_capacity, uint64_t* out_nvertices,
+                           uint64_t* out_ntriangles, uint64_t* opt_out_seed_cube);
+/* The seed search's table for queue_max (host only): out_offsets receives 3 int32 (di, dj, dk) per cube, in first-pop order;
+ * *out_count (cubes) and *out_bounded (1: the queue reaches queue_max, 0: unbounded) are always set; PCPX_ERR_CAPACITY if
+ * out_offsets is NULL or holds fewer than *out_count cubes. */
+int pcpx_surface_nets_search_order(uint64_t queue_max, int32_t* out_offsets, uint64_t capacity, uint64_t* out_count, int* out_bounded);
 /* The example's signed-distance function at every corner of `grid`: the nearest indexed point j of the corner (1-NN with the
  * eps-box exclusion, as nearest_neighbours(coords, 1)) and dot(c - o_j, n_j) with the plane (o, n) of point j -- d_centroids,
  * d_normals: n x 3 device arrays in input order, e.g. from pcpx_neighbourhoods_self_dev.  Corners outside the index's voxel

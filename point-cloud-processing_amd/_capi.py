@@ -156,6 +156,13 @@ SIGNATURES = {
                                               C.c_void_p, C.c_uint64, u64p, u64p, f32p]),
     "pcpx_surface_nets": (C.c_int, [C.c_void_p, C.POINTER(Grid3d), C.c_float, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                     u64p, u64p]),
+    "pcpx_surface_nets_hint_dev": (C.c_int, [C.c_void_p, C.POINTER(Grid3d), C.c_float, f32p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_uint64, C.c_void_p, C.c_uint64, u64p, u64p, u64p]),
+    "pcpx_surface_nets_hint_timed_dev": (C.c_int, [C.c_void_p, C.POINTER(Grid3d), C.c_float, f32p, C.c_uint64, C.c_int, C.c_void_p,
+                                                   C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u64p, u64p, u64p, f32p, u32p]),
+    "pcpx_surface_nets_hint": (C.c_int, [C.c_void_p, C.POINTER(Grid3d), C.c_float, f32p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64,
+                                         C.c_void_p, C.c_uint64, u64p, u64p, u64p]),
+    "pcpx_surface_nets_search_order": (C.c_int, [C.c_uint64, C.c_void_p, C.c_uint64, u64p, C.POINTER(C.c_int)]),
     "pcpx_tangent_plane_sdf_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Grid3d), C.c_float, C.c_void_p]),
     "pcpx_reconstruct_surface": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, u64p, C.c_float, C.c_void_p, C.c_uint64, C.c_void_p,
                                            C.c_uint64, u64p, u64p, C.c_void_p, C.c_void_p, C.POINTER(Grid3d)]),

@@ -13,9 +13,17 @@
 //   3. one thread per active cube: triangle count;  scan;  the same thread again: the triangles, in (cube, quad 0..2,
 //      triangle 0..1) order.
 // The vertex arithmetic is the reference's operation for operation; the build's -ffp-contract=off keeps it unfused.
+//
+// Hint-seeded surface nets (:653-1119 of the reference): the same passes restricted to one connected
+// component of the active cubes, found by a table-driven seed search and union-find labelling.
 #include "pcpx_internal.h"
 
 #include <algorithm>
+#include <array>
+#include <cmath>
+#include <deque>
+#include <map>
+#include <unordered_set>
 
 namespace pcpx {
 
@@ -360,6 +368,170 @@ __global__ __launch_bounds__(SN_BLOCK) void k_sn_triangles(GridDev g, u32 nvert,
     }
 }
 
+// ---- hint-seeded surface nets: the seed, the components of the active cubes, the restriction -------------------------------
+
+// the reference's adjacent_cubes_of_edges (surface_nets.hpp:853-866): the three other cubes around edge e of a cube
+__constant__ signed char c_edge_cubes[12][3][3] = {
+    {{0, -1, 0}, {0, -1, -1}, {0, 0, -1}}, {{1, 0, 0}, {1, 0, -1}, {0, 0, -1}},  {{0, 1, 0}, {0, 1, -1}, {0, 0, -1}},
+    {{-1, 0, 0}, {-1, 0, -1}, {0, 0, -1}}, {{0, -1, 0}, {0, -1, 1}, {0, 0, 1}},  {{1, 0, 0}, {1, 0, 1}, {0, 0, 1}},
+    {{0, 1, 0}, {0, 1, 1}, {0, 0, 1}},     {{-1, 0, 0}, {-1, 0, 1}, {0, 0, 1}},  {{-1, 0, 0}, {-1, -1, 0}, {0, -1, 0}},
+    {{1, 0, 0}, {1, -1, 0}, {0, -1, 0}},   {{1, 0, 0}, {1, 1, 0}, {0, 1, 0}},    {{-1, 0, 0}, {-1, 1, 0}, {0, 1, 0}},
+};
+
+// the seed: the first table entry (offsets from the hint cube h, in the reference's first-pop order) that is an active cube of
+// the grid.  One block; each thread stops at its own first hit, so the block minimum of the ranks is the first hit overall.
+// seed[0] = its cube, or UINT64_MAX.
+__global__ __launch_bounds__(SN_BLOCK) void k_hint_seed(GridDev g, const int* __restrict__ offsets, u32 n, long long hx, long long hy,
+                                                        long long hz, const u32* __restrict__ map, unsigned long long* __restrict__ seed)
+{
+    __shared__ u32 best[SN_BLOCK];
+    u32 mine = NO_VERTEX;
+    for (u32 r = threadIdx.x; r < n; r += SN_BLOCK) {
+        const long long i = hx + offsets[3 * r], j = hy + offsets[3 * r + 1], k = hz + offsets[3 * r + 2];
+        if (i < 0 || j < 0 || k < 0 || i >= g.sx || j >= g.sy || k >= g.sz) continue;
+        const u32 c = static_cast<u32>(i) + static_cast<u32>(j) * g.sx + static_cast<u32>(k) * (g.sx * g.sy);
+        if (map[c] != NO_VERTEX) {
+            mine = r;
+            break;
+        }
+    }
+    best[threadIdx.x] = mine;
+    __syncthreads();
+    for (int w = SN_BLOCK / 2; w > 0; w >>= 1) {
+        if (threadIdx.x < w) best[threadIdx.x] = min(best[threadIdx.x], best[threadIdx.x + w]);
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const u32 r = best[0];
+    if (r == NO_VERTEX) {
+        seed[0] = ~0ull;
+        return;
+    }
+    const u32 i = static_cast<u32>(hx + offsets[3 * r]), j = static_cast<u32>(hy + offsets[3 * r + 1]), k = static_cast<u32>(hz + offsets[3 * r + 2]);
+    seed[0] = i + j * g.sx + k * (g.sx * g.sy);
+}
+
+// without a bound and with no table entry active: seed[1] = min over the active cubes of (Manhattan distance to the hint cube
+// clamped into the grid) << 32 | cube -- the nearest to the hint cube itself, as the offset from the clamp is the same for every
+// cube.  Does nothing when k_hint_seed found a seed (seed[0], written by the launch before).  One atomic per block.
+__global__ __launch_bounds__(SN_BLOCK) void k_hint_nearest(GridDev g, u32 nvert, const u32* __restrict__ active, u32 cx, u32 cy, u32 cz,
+                                                           unsigned long long* __restrict__ seed)
+{
+    __shared__ unsigned long long best[SN_BLOCK];
+    unsigned long long mine = ~0ull;
+    if (seed[0] == ~0ull) {
+        for (u64 v = static_cast<u64>(blockIdx.x) * SN_BLOCK + threadIdx.x; v < nvert; v += static_cast<u64>(gridDim.x) * SN_BLOCK) {
+            const u32 c = active[v];
+            u32 i, j, k;
+            cube_of(g, c, i, j, k);
+            const u64 d = static_cast<u64>(i > cx ? i - cx : cx - i) + (j > cy ? j - cy : cy - j) + (k > cz ? k - cz : cz - k);
+            mine = min(mine, static_cast<unsigned long long>(d << 32 | c));
+        }
+    }
+    best[threadIdx.x] = mine;
+    __syncthreads();
+    for (int w = SN_BLOCK / 2; w > 0; w >>= 1) {
+        if (threadIdx.x < w) best[threadIdx.x] = min(best[threadIdx.x], best[threadIdx.x + w]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && best[0] != ~0ull) atomicMin(seed + 1, best[0]);
+}
+
+// Connected components of the active cubes (two are adjacent iff they share a bipolar edge) by union-find over active ranks,
+// in the style of ECL-CC: parent[v] <= v always, a root is its own parent, a hook links the larger of two roots under the
+// smaller with a CAS.  So every root is the smallest rank of its tree and the final label of a component is its smallest
+// active rank, whatever the order the hooks ran in.
+//
+// Coherence: the parent words are written by other workgroups, on other XCDs, within the hook launch, so every access to
+// them there is an agent-scope atomic (relaxed: no other data is handed over through them).  Path halving stores an
+// ancestor over a non-root's parent; any value ever held by parent[x] is an ancestor of x and stays one, so a stale or
+// overwritten halving store only lengthens a later walk.  A CAS succeeds only on a word that still holds its own index (a
+// root); when it fails, both sides climb again from what it returned.
+__device__ __forceinline__ u32 cc_load(const u32* p)
+{
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ u32 cc_root(u32* parent, u32 x)
+{
+    u32 cur = cc_load(parent + x);
+    if (cur != x) {
+        u32 prev = x, next;
+        while (cur > (next = cc_load(parent + cur))) {
+            __hip_atomic_store(parent + prev, next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            prev = cur;
+            cur = next;
+        }
+    }
+    return cur;
+}
+
+__global__ __launch_bounds__(SN_BLOCK) void k_cc_init(u32 nvert, u32* __restrict__ parent)
+{
+    for (u64 v = static_cast<u64>(blockIdx.x) * SN_BLOCK + threadIdx.x; v < nvert; v += static_cast<u64>(gridDim.x) * SN_BLOCK)
+        parent[v] = static_cast<u32>(v);
+}
+
+// one thread per active cube: the in-grid cubes around its bipolar edges that come later in cube order (the earlier ones
+// hook this pair from their side), each once -- a face neighbour shares four edges -- then a union with each
+__global__ __launch_bounds__(SN_BLOCK) void k_cc_hook(GridDev g, u32 nvert, const float* __restrict__ field, float iso,
+                                                      const u32* __restrict__ active, const u32* __restrict__ map, u32* parent)
+{
+    for (u64 v64 = static_cast<u64>(blockIdx.x) * SN_BLOCK + threadIdx.x; v64 < nvert; v64 += static_cast<u64>(gridDim.x) * SN_BLOCK) {
+        const u32 v = static_cast<u32>(v64), c = active[v];
+        u32 i, j, k;
+        cube_of(g, c, i, j, k);
+        float s[8];
+        cube_corners(g, field, i, j, k, s);
+        // bit (di+1) + 3(dj+1) + 9(dk+1) of the 3x3x3 block around the cube; bits 14..26 are the later cubes
+        u32 around = 0;
+        for (int e = 0; e < 12; ++e) {
+            if ((s[c_edges[e][0]] >= iso) == (s[c_edges[e][1]] >= iso)) continue;
+            for (int q = 0; q < 3; ++q)
+                around |= 1u << ((c_edge_cubes[e][q][0] + 1) + 3 * (c_edge_cubes[e][q][1] + 1) + 9 * (c_edge_cubes[e][q][2] + 1));
+        }
+        around &= ~((1u << 14) - 1);
+        while (around) {
+            const int b = __builtin_ctz(around);
+            around &= around - 1;
+            const int di = b % 3 - 1, dj = (b / 3) % 3 - 1, dk = b / 9 - 1;
+            if ((di < 0 && i == 0) || (dj < 0 && j == 0) || (di > 0 && i + 1 == g.sx) || (dj > 0 && j + 1 == g.sy) || (dk > 0 && k + 1 == g.sz))
+                continue;  // (outside the grid; dk >= 0 here)
+            const u32 u = map[(i + di) + (j + dj) * g.sx + (k + dk) * (g.sx * g.sy)];  // (a cube on a bipolar edge is active)
+            if (u == NO_VERTEX) continue;
+            u32 a = cc_root(parent, v), r = cc_root(parent, u);
+            while (a != r) {
+                u32 lo = a < r ? a : r, hi = a < r ? r : a;
+                if (__hip_atomic_compare_exchange_strong(parent + hi, &hi, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                    break;
+                a = cc_root(parent, hi);  // hi now holds the parent it was given meanwhile
+                r = cc_root(parent, lo);
+            }
+        }
+    }
+}
+
+// parent[v] = the root of v (a launch after the hooks: the roots are fixed, and the words this launch rewrites only ever
+// change from one ancestor to a higher one, so the walks read them with the same atomics and end at the same root)
+__global__ __launch_bounds__(SN_BLOCK) void k_cc_flatten(u32 nvert, u32* parent)
+{
+    for (u64 v = static_cast<u64>(blockIdx.x) * SN_BLOCK + threadIdx.x; v < nvert; v += static_cast<u64>(gridDim.x) * SN_BLOCK) {
+        const u32 r = cc_root(parent, static_cast<u32>(v));
+        __hip_atomic_store(parent + v, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// flag[c] = cube c is active and in the seed's component (label = the seed's root rank)
+__global__ __launch_bounds__(SN_BLOCK) void k_cc_restrict(u32 ncubes, const u32* __restrict__ map, const u32* __restrict__ label, u32 seed_cube,
+                                                          u32* __restrict__ flag)
+{
+    const u32 want = label[map[seed_cube]];
+    for (u64 c = static_cast<u64>(blockIdx.x) * SN_BLOCK + threadIdx.x; c < ncubes; c += static_cast<u64>(gridDim.x) * SN_BLOCK) {
+        const u32 m = map[c];
+        flag[c] = m != NO_VERTEX && label[m] == want ? 1u : 0u;
+    }
+}
+
 int grid_to_dev(const pcpx_grid3d& g, GridDev& d, u64& ncubes)
 {
     ncubes = 0;
@@ -384,6 +556,87 @@ int check_surface_grid(const pcpx_grid3d& grid)
     return grid_to_dev(grid, g, ncubes);
 }
 
+// events of a timed call, destroyed on every return
+struct Events {
+    hipEvent_t e[6] = {};
+    int n = 0;
+    int create(int count)
+    {
+        for (; n < count; ++n) PCPX_HIP(hipEventCreate(&e[n]));
+        return PCPX_OK;
+    }
+    ~Events()
+    {
+        for (int q = 0; q < n; ++q) (void)hipEventDestroy(e[q]);
+    }
+};
+
+// pass 1: flags, scanned in place into vertex offsets (ncubes + 1 entries); the number of active cubes in *nv.  ev_scanned (may
+// be null) is recorded after the scan, ahead of the count's read-back.
+int active_offsets(const GridDev& g, u64 ncubes, const float* d_field, float iso, hipStream_t s, u32* vofs, u32* sums, hipEvent_t ev_scanned,
+                   u64* nv)
+{
+    PCPX_HIP(hipMemsetAsync(vofs + ncubes, 0, sizeof(u32), s));
+    k_sn_flags<<<blocks_for(ncubes), SN_BLOCK, 0, s>>>(g, static_cast<u32>(ncubes), d_field, iso, vofs);
+    PCPX_HIP(hipGetLastError());
+    const int st = exclusive_scan_in_place<u32>(vofs, ncubes + 1, sums, s);
+    if (st != PCPX_OK) return st;
+    if (ev_scanned) PCPX_HIP(hipEventRecord(ev_scanned, s));
+    u32 nv32 = 0;
+    PCPX_HIP(hipMemcpyAsync(&nv32, vofs + ncubes, sizeof(u32), hipMemcpyDeviceToHost, s));
+    PCPX_HIP(hipStreamSynchronize(s));
+    *nv = nv32;
+    return PCPX_OK;
+}
+
+// passes 2 and 3 over the cubes that `vofs` selects (nv of them): the map, the list, the vertices and the triangles, with the
+// capacity protocol of surface_nets_device.  ev_vertices / ev_end (may be null) are recorded after the vertices and at the end.
+int mesh_selected(const GridDev& g, u64 ncubes, const float* d_field, float iso, hipStream_t s, DevPool& pool, const u32* vofs, u32* map,
+                  u64 nv, float* d_out_xyz, u64 vertex_capacity, u32* d_out_tri, u64 triangle_capacity, u64* out_nt, hipEvent_t ev_vertices,
+                  hipEvent_t ev_end)
+{
+    int st;
+    const u32 nc = static_cast<u32>(ncubes), nv32 = static_cast<u32>(nv);
+    // pass 2: the map, the active cubes, and the vertices if they fit
+    DevBuf active(pool), tofs(pool), tsums(pool);
+    const u64 tiles_v = (nv + 1 + SCAN_TILE - 1) / SCAN_TILE;
+    if ((st = active.alloc(nv * sizeof(u32))) != PCPX_OK || (st = tofs.alloc((nv + 1) * sizeof(u64))) != PCPX_OK ||
+        (st = tsums.alloc(std::max<u64>(tiles_v, 64) * sizeof(u64))) != PCPX_OK)
+        return st;
+    const bool write_vertices = d_out_xyz && nv <= vertex_capacity;
+    k_sn_vertices<<<blocks_for(ncubes), SN_BLOCK, 0, s>>>(g, nc, d_field, iso, vofs, map, active.as<u32>(), write_vertices ? d_out_xyz : nullptr);
+    PCPX_HIP(hipGetLastError());
+    if (ev_vertices) PCPX_HIP(hipEventRecord(ev_vertices, s));
+    // pass 3: triangle counts of the active cubes, scanned; then the triangles if they fit
+    u64 nt = 0;
+    if (nv > 0) {
+        PCPX_HIP(hipMemsetAsync(tofs.as<u64>() + nv, 0, sizeof(u64), s));
+        k_sn_tri_count<<<blocks_for(nv), SN_BLOCK, 0, s>>>(g, nv32, active.as<u32>(), map, tofs.as<u64>());
+        PCPX_HIP(hipGetLastError());
+        if ((st = exclusive_scan_in_place<u64>(tofs.as<u64>(), nv + 1, tsums.as<u64>(), s)) != PCPX_OK) return st;
+        PCPX_HIP(hipMemcpyAsync(&nt, tofs.as<u64>() + nv, sizeof(u64), hipMemcpyDeviceToHost, s));
+        PCPX_HIP(hipStreamSynchronize(s));
+    }
+    *out_nt = nt;
+    const bool write_triangles = d_out_tri && nt <= triangle_capacity;
+    if (nt > 0 && write_triangles) {
+        k_sn_triangles<<<blocks_for(nv), SN_BLOCK, 0, s>>>(g, nv32, d_field, active.as<u32>(), map, tofs.as<u64>(), d_out_tri);
+        PCPX_HIP(hipGetLastError());
+    }
+    if (ev_end) {
+        PCPX_HIP(hipEventRecord(ev_end, s));
+        PCPX_HIP(hipEventSynchronize(ev_end));
+    }
+    // the scratch goes back to the pool on return: nothing that reads it may still be queued
+    PCPX_HIP(hipStreamSynchronize(s));
+    if ((nv > 0 && !write_vertices) || (nt > 0 && !write_triangles)) {
+        set_error("pcpx_surface_nets: the mesh has %llu vertices and %llu triangles", static_cast<unsigned long long>(nv),
+                  static_cast<unsigned long long>(nt));
+        return PCPX_ERR_CAPACITY;
+    }
+    return PCPX_OK;
+}
+
 int surface_nets_device(const float* d_field, const pcpx_grid3d& grid, float iso, hipStream_t s, DevPool& pool, float* d_out_xyz,
                         u64 vertex_capacity, u32* d_out_tri, u64 triangle_capacity, u64* out_nv, u64* out_nt, SurfaceNetsTimes* times)
 {
@@ -397,79 +650,204 @@ int surface_nets_device(const float* d_field, const pcpx_grid3d& grid, float iso
         set_error("pcpx_surface_nets_dev: null field");
         return PCPX_ERR_INVALID;
     }
-    const u32 nc = static_cast<u32>(ncubes);
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    if (times) {
-        for (auto& e : ev) PCPX_HIP(hipEventCreate(&e));
-    }
-    struct EventsGone {
-        hipEvent_t* e;
-        ~EventsGone()
-        {
-            for (int q = 0; q < 4; ++q)
-                if (e[q]) (void)hipEventDestroy(e[q]);
-        }
-    } events_gone{ev};
-    // pass 1: flags, scanned in place into vertex offsets (ncubes + 1 entries)
+    Events ev;
+    if (times && (st = ev.create(4)) != PCPX_OK) return st;
     DevBuf vofs(pool), sums(pool), map(pool);
     const u64 tiles_c = (ncubes + 1 + SCAN_TILE - 1) / SCAN_TILE;
     if ((st = vofs.alloc((ncubes + 1) * sizeof(u32))) != PCPX_OK || (st = map.alloc(ncubes * sizeof(u32))) != PCPX_OK ||
         (st = sums.alloc(std::max<u64>(tiles_c, 64) * sizeof(u64))) != PCPX_OK)
         return st;
-    if (times) PCPX_HIP(hipEventRecord(ev[0], s));
-    PCPX_HIP(hipMemsetAsync(vofs.as<u32>() + ncubes, 0, sizeof(u32), s));
-    k_sn_flags<<<blocks_for(ncubes), SN_BLOCK, 0, s>>>(g, nc, d_field, iso, vofs.as<u32>());
-    PCPX_HIP(hipGetLastError());
-    if ((st = exclusive_scan_in_place<u32>(vofs.as<u32>(), ncubes + 1, sums.as<u32>(), s)) != PCPX_OK) return st;
-    if (times) PCPX_HIP(hipEventRecord(ev[1], s));
-    u32 nv32 = 0;
-    PCPX_HIP(hipMemcpyAsync(&nv32, vofs.as<u32>() + ncubes, sizeof(u32), hipMemcpyDeviceToHost, s));
-    PCPX_HIP(hipStreamSynchronize(s));
-    const u64 nv = nv32;
-    *out_nv = nv;
-    // pass 2: the map, the active cubes, and the vertices if they fit
-    DevBuf active(pool), tofs(pool), tsums(pool);
-    const u64 tiles_v = (nv + 1 + SCAN_TILE - 1) / SCAN_TILE;
-    if ((st = active.alloc(nv * sizeof(u32))) != PCPX_OK || (st = tofs.alloc((nv + 1) * sizeof(u64))) != PCPX_OK ||
-        (st = tsums.alloc(std::max<u64>(tiles_v, 64) * sizeof(u64))) != PCPX_OK)
+    if (times) PCPX_HIP(hipEventRecord(ev.e[0], s));
+    if ((st = active_offsets(g, ncubes, d_field, iso, s, vofs.as<u32>(), sums.as<u32>(), ev.e[1], out_nv)) != PCPX_OK) return st;
+    st = mesh_selected(g, ncubes, d_field, iso, s, pool, vofs.as<u32>(), map.as<u32>(), *out_nv, d_out_xyz, vertex_capacity, d_out_tri,
+                       triangle_capacity, out_nt, ev.e[2], ev.e[3]);
+    if (times && (st == PCPX_OK || st == PCPX_ERR_CAPACITY)) {
+        PCPX_HIP(hipEventElapsedTime(&times->flags_ms, ev.e[0], ev.e[1]));
+        PCPX_HIP(hipEventElapsedTime(&times->vertices_ms, ev.e[1], ev.e[2]));
+        PCPX_HIP(hipEventElapsedTime(&times->triangles_ms, ev.e[2], ev.e[3]));
+    }
+    return st;
+}
+
+// ---- hint-seeded surface nets (surface_nets.hpp:653-1119 of the reference; the contract is DESIGN.md section 15) ------------
+
+namespace {
+
+constexpr u64 HINT_POP_CAP = 1ull << 20;  // pops of the simulated queue after which the search counts as unbounded
+
+struct SearchOrder {
+    std::vector<int> offsets;  // 3 per cube, in first-pop order
+    bool bounded = false;
+};
+
+// The reference's first search (surface_nets.hpp:773-842) on an unbounded lattice with no active cube: pop, mark visited, push
+// the six neighbours not yet visited (+x, -x, +y, -y, +z, -z), duplicates and all; before every pop, stop if the queue holds
+// exactly queue_max cubes.  Returns the distinct cubes popped before the stop, or before HINT_POP_CAP pops (unbounded).
+SearchOrder simulate_search(u64 queue_max)
+{
+    constexpr int B = 21;  // offsets stay within +-HINT_POP_CAP: 21 bits per axis, biased
+    const auto key = [](long long i, long long j, long long k) {
+        return (static_cast<u64>(i + (1 << 20)) << (2 * B)) | (static_cast<u64>(j + (1 << 20)) << B) | static_cast<u64>(k + (1 << 20));
+    };
+    SearchOrder out;
+    std::deque<std::array<int, 3>> queue;
+    std::unordered_set<u64> visited;
+    queue.push_back({0, 0, 0});
+    for (u64 pops = 0; pops < HINT_POP_CAP; ++pops) {
+        if (queue.size() == queue_max) {
+            out.bounded = true;
+            break;
+        }
+        const std::array<int, 3> c = queue.front();
+        queue.pop_front();
+        if (visited.insert(key(c[0], c[1], c[2])).second) out.offsets.insert(out.offsets.end(), c.begin(), c.end());
+        const std::array<int, 3> nb[6] = {{c[0] + 1, c[1], c[2]}, {c[0] - 1, c[1], c[2]}, {c[0], c[1] + 1, c[2]},
+                                          {c[0], c[1] - 1, c[2]}, {c[0], c[1], c[2] + 1}, {c[0], c[1], c[2] - 1}};
+        for (const auto& n : nb)
+            if (!visited.count(key(n[0], n[1], n[2]))) queue.push_back(n);
+    }
+    return out;
+}
+
+// the table of queue_max, simulated once per process and value
+const SearchOrder& search_order(u64 queue_max)
+{
+    static std::mutex mu;
+    static std::map<u64, SearchOrder> tables;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = tables.find(queue_max);
+    if (it == tables.end()) it = tables.emplace(queue_max, simulate_search(queue_max)).first;
+    return it->second;
+}
+
+int surface_nets_hint_device(const float* d_field, const pcpx_grid3d& grid, float iso, const float hint[3], u64 queue_max, hipStream_t s,
+                             DevPool& pool, float* d_out_xyz, u64 vertex_capacity, u32* d_out_tri, u64 triangle_capacity, u64* out_nv,
+                             u64* out_nt, u64* out_seed, float* phase_ms, u32* rounds)
+{
+    *out_nv = 0;
+    *out_nt = 0;
+    *out_seed = UINT64_MAX;
+    if (rounds) *rounds = 0;
+    if (!std::isfinite(hint[0]) || !std::isfinite(hint[1]) || !std::isfinite(hint[2])) {
+        set_error("pcpx_surface_nets_hint: the hint is not finite");
+        return PCPX_ERR_INVALID;
+    }
+    GridDev g{};
+    u64 ncubes = 0;
+    int st = grid_to_dev(grid, g, ncubes);
+    if (st != PCPX_OK || ncubes == 0) return st;
+    if (!d_field) {
+        set_error("pcpx_surface_nets_hint_dev: null field");
+        return PCPX_ERR_INVALID;
+    }
+    // the hint cube: (p - o) / d per axis in float as get_grid_point_of, truncated -- floored, so negative values are defined too;
+    // clamped far beyond the reach of any table so that the offsets below cannot overflow
+    long long h[3];
+    const float o[3] = {grid.x, grid.y, grid.z}, d[3] = {grid.dx, grid.dy, grid.dz};
+    const u32 sz[3] = {g.sx, g.sy, g.sz};
+    u32 hc[3];
+    for (int a = 0; a < 3; ++a) {
+        const float q = (hint[a] - o[a]) / d[a];
+        if (std::isnan(q)) {
+            set_error("pcpx_surface_nets_hint: the hint's grid coordinate is NaN (a zero voxel size)");
+            return PCPX_ERR_INVALID;
+        }
+        const double lim = 1099511627776.0;  // 2^40
+        h[a] = static_cast<long long>(std::min(lim, std::max(-lim, std::floor(static_cast<double>(q)))));
+        hc[a] = static_cast<u32>(std::min<long long>(std::max<long long>(h[a], 0), sz[a] - 1));
+    }
+    const SearchOrder& order = search_order(queue_max);
+    const u64 table = order.offsets.size() / 3;
+
+    Events ev;
+    if (phase_ms && (st = ev.create(6)) != PCPX_OK) return st;
+    const auto mark = [&](int q) -> int {
+        if (phase_ms) PCPX_HIP(hipEventRecord(ev.e[q], s));
+        return PCPX_OK;
+    };
+    DevBuf vofs(pool), sums(pool), map(pool), active(pool), parent(pool), seed(pool), offs(pool);
+    const u64 tiles_c = (ncubes + 1 + SCAN_TILE - 1) / SCAN_TILE;
+    if ((st = vofs.alloc((ncubes + 1) * sizeof(u32))) != PCPX_OK || (st = map.alloc(ncubes * sizeof(u32))) != PCPX_OK ||
+        (st = sums.alloc(std::max<u64>(tiles_c, 64) * sizeof(u64))) != PCPX_OK || (st = seed.alloc(2 * sizeof(u64))) != PCPX_OK ||
+        (st = offs.alloc(std::max<u64>(table, 1) * 3 * sizeof(int))) != PCPX_OK)
         return st;
-    const bool write_vertices = d_out_xyz && nv <= vertex_capacity;
-    k_sn_vertices<<<blocks_for(ncubes), SN_BLOCK, 0, s>>>(g, nc, d_field, iso, vofs.as<u32>(), map.as<u32>(), active.as<u32>(),
-                                                          write_vertices ? d_out_xyz : nullptr);
+    // phase 1: the active cubes -- offsets, then the dense cube -> active rank map and the list
+    if ((st = mark(0)) != PCPX_OK) return st;
+    u64 nv = 0;
+    if ((st = active_offsets(g, ncubes, d_field, iso, s, vofs.as<u32>(), sums.as<u32>(), nullptr, &nv)) != PCPX_OK) return st;
+    if ((st = active.alloc(std::max<u64>(nv, 1) * sizeof(u32))) != PCPX_OK || (st = parent.alloc(std::max<u64>(nv, 1) * sizeof(u32))) != PCPX_OK)
+        return st;
+    k_sn_vertices<<<blocks_for(ncubes), SN_BLOCK, 0, s>>>(g, static_cast<u32>(ncubes), d_field, iso, vofs.as<u32>(), map.as<u32>(),
+                                                          active.as<u32>(), nullptr);
     PCPX_HIP(hipGetLastError());
-    if (times) PCPX_HIP(hipEventRecord(ev[2], s));
-    // pass 3: triangle counts of the active cubes, scanned; then the triangles if they fit
-    u64 nt = 0;
+    if ((st = mark(1)) != PCPX_OK) return st;
+    // phase 2: the seed
+    u64 found[2] = {UINT64_MAX, UINT64_MAX};
     if (nv > 0) {
-        PCPX_HIP(hipMemsetAsync(tofs.as<u64>() + nv, 0, sizeof(u64), s));
-        k_sn_tri_count<<<blocks_for(nv), SN_BLOCK, 0, s>>>(g, nv32, active.as<u32>(), map.as<u32>(), tofs.as<u64>());
-        PCPX_HIP(hipGetLastError());
-        if ((st = exclusive_scan_in_place<u64>(tofs.as<u64>(), nv + 1, tsums.as<u64>(), s)) != PCPX_OK) return st;
-        PCPX_HIP(hipMemcpyAsync(&nt, tofs.as<u64>() + nv, sizeof(u64), hipMemcpyDeviceToHost, s));
+        PCPX_HIP(hipMemsetAsync(seed.p, 0xFF, 2 * sizeof(u64), s));
+        if (table > 0) {
+            if ((st = upload_pageable(offs.p, order.offsets.data(), table * 3 * sizeof(int), s)) != PCPX_OK) return st;
+            k_hint_seed<<<1, SN_BLOCK, 0, s>>>(g, offs.as<int>(), static_cast<u32>(table), h[0], h[1], h[2], map.as<u32>(),
+                                               seed.as<unsigned long long>());
+            PCPX_HIP(hipGetLastError());
+        }
+        if (!order.bounded) {
+            k_hint_nearest<<<blocks_for(nv), SN_BLOCK, 0, s>>>(g, static_cast<u32>(nv), active.as<u32>(), hc[0], hc[1], hc[2],
+                                                               seed.as<unsigned long long>());
+            PCPX_HIP(hipGetLastError());
+        }
+        PCPX_HIP(hipMemcpyAsync(found, seed.p, sizeof(found), hipMemcpyDeviceToHost, s));
         PCPX_HIP(hipStreamSynchronize(s));
     }
-    *out_nt = nt;
-    const bool write_triangles = d_out_tri && nt <= triangle_capacity;
-    if (nt > 0 && write_triangles) {
-        k_sn_triangles<<<blocks_for(nv), SN_BLOCK, 0, s>>>(g, nv32, d_field, active.as<u32>(), map.as<u32>(), tofs.as<u64>(), d_out_tri);
+    const u64 seed_cube = found[0] != UINT64_MAX ? found[0] : (found[1] != UINT64_MAX ? (found[1] & 0xFFFFFFFFull) : UINT64_MAX);
+    *out_seed = seed_cube;
+    if ((st = mark(2)) != PCPX_OK) return st;
+    // phase 3: the components, and phase 4: the restriction to the seed's (no seed: the whole grid, vofs as it stands)
+    u64 nsel = nv;
+    if (seed_cube != UINT64_MAX) {
+        const u32 nv32 = static_cast<u32>(nv);
+        k_cc_init<<<blocks_for(nv), SN_BLOCK, 0, s>>>(nv32, parent.as<u32>());
+        k_cc_hook<<<blocks_for(nv), SN_BLOCK, 0, s>>>(g, nv32, d_field, iso, active.as<u32>(), map.as<u32>(), parent.as<u32>());
+        k_cc_flatten<<<blocks_for(nv), SN_BLOCK, 0, s>>>(nv32, parent.as<u32>());
         PCPX_HIP(hipGetLastError());
+        if (rounds) *rounds = 1;  // union-find: one hook launch, whatever the component's diameter
+        if ((st = mark(3)) != PCPX_OK) return st;
+        PCPX_HIP(hipMemsetAsync(vofs.as<u32>() + ncubes, 0, sizeof(u32), s));
+        k_cc_restrict<<<blocks_for(ncubes), SN_BLOCK, 0, s>>>(static_cast<u32>(ncubes), map.as<u32>(), parent.as<u32>(),
+                                                              static_cast<u32>(seed_cube), vofs.as<u32>());
+        PCPX_HIP(hipGetLastError());
+        if ((st = exclusive_scan_in_place<u32>(vofs.as<u32>(), ncubes + 1, sums.as<u32>(), s)) != PCPX_OK) return st;
+        u32 n32 = 0;
+        PCPX_HIP(hipMemcpyAsync(&n32, vofs.as<u32>() + ncubes, sizeof(u32), hipMemcpyDeviceToHost, s));
+        PCPX_HIP(hipStreamSynchronize(s));
+        nsel = n32;
+    } else if ((st = mark(3)) != PCPX_OK) {
+        return st;
     }
-    if (times) {
-        PCPX_HIP(hipEventRecord(ev[3], s));
-        PCPX_HIP(hipEventSynchronize(ev[3]));
-        PCPX_HIP(hipEventElapsedTime(&times->flags_ms, ev[0], ev[1]));
-        PCPX_HIP(hipEventElapsedTime(&times->vertices_ms, ev[1], ev[2]));
-        PCPX_HIP(hipEventElapsedTime(&times->triangles_ms, ev[2], ev[3]));
-    }
-    // the scratch goes back to the pool on return: nothing that reads it may still be queued
-    PCPX_HIP(hipStreamSynchronize(s));
-    if ((nv > 0 && !write_vertices) || (nt > 0 && !write_triangles)) {
-        set_error("pcpx_surface_nets: the mesh has %llu vertices and %llu triangles", static_cast<unsigned long long>(nv),
-                  static_cast<unsigned long long>(nt));
+    *out_nv = nsel;
+    // phases 4 (the vertices) and 5 (the triangles): the whole-grid passes over the selected cubes
+    st = mesh_selected(g, ncubes, d_field, iso, s, pool, vofs.as<u32>(), map.as<u32>(), nsel, d_out_xyz, vertex_capacity, d_out_tri,
+                       triangle_capacity, out_nt, phase_ms ? ev.e[4] : nullptr, phase_ms ? ev.e[5] : nullptr);
+    if (phase_ms && (st == PCPX_OK || st == PCPX_ERR_CAPACITY))
+        for (int q = 0; q < 5; ++q) PCPX_HIP(hipEventElapsedTime(&phase_ms[q], ev.e[q], ev.e[q + 1]));
+    return st;
+}
+
+int surface_nets_search_order(u64 queue_max, int* out, u64 capacity, u64* out_count, int* out_bounded)
+{
+    const SearchOrder& order = search_order(queue_max);
+    *out_count = order.offsets.size() / 3;
+    *out_bounded = order.bounded ? 1 : 0;
+    if (*out_count == 0) return PCPX_OK;
+    if (!out || capacity < *out_count) {
+        set_error("pcpx_surface_nets_search_order: the table has %llu entries", static_cast<unsigned long long>(*out_count));
         return PCPX_ERR_CAPACITY;
     }
+    std::copy(order.offsets.begin(), order.offsets.end(), out);
     return PCPX_OK;
 }
+
+}  // namespace
 
 int tangent_plane_sdf_device(Index& ix, const float* d_centroids, const float* d_normals, const pcpx_grid3d& grid, float eps, float* d_field)
 {
@@ -586,6 +964,77 @@ int pcpx_surface_nets(const float* field, const pcpx_grid3d* grid, float isovalu
         PCPX_HIP(hipStreamSynchronize(s));
         return PCPX_OK;
     });
+}
+
+int pcpx_surface_nets_hint_timed_dev(const float* d_field, const pcpx_grid3d* grid, float isovalue, const float hint[3], uint64_t queue_max,
+                                     int device, void* stream, float* d_out_xyz, uint64_t vertex_capacity, uint32_t* d_out_tri,
+                                     uint64_t triangle_capacity, uint64_t* out_nvertices, uint64_t* out_ntriangles, uint64_t* opt_out_seed_cube,
+                                     float out_phase_ms[5], uint32_t* opt_out_rounds)
+{
+    if (opt_out_seed_cube) *opt_out_seed_cube = UINT64_MAX;
+    if (!grid || !hint || !out_nvertices || !out_ntriangles) return PCPX_ERR_INVALID;
+    *out_nvertices = *out_ntriangles = 0;
+    return on_shared(device, "pcpx_surface_nets_hint_dev", [&](DeviceShared& sh) -> int {
+        u64 seed = UINT64_MAX;
+        const int r = surface_nets_hint_device(d_field, *grid, isovalue, hint, queue_max, static_cast<hipStream_t>(stream), sh.pool, d_out_xyz,
+                                               vertex_capacity, d_out_tri, triangle_capacity, out_nvertices, out_ntriangles, &seed, out_phase_ms,
+                                               opt_out_rounds);
+        if (opt_out_seed_cube) *opt_out_seed_cube = seed;
+        return r;
+    });
+}
+
+int pcpx_surface_nets_hint_dev(const float* d_field, const pcpx_grid3d* grid, float isovalue, const float hint[3], uint64_t queue_max, int device,
+                               void* stream, float* d_out_xyz, uint64_t vertex_capacity, uint32_t* d_out_tri, uint64_t triangle_capacity,
+                               uint64_t* out_nvertices, uint64_t* out_ntriangles, uint64_t* opt_out_seed_cube)
+{
+    return pcpx_surface_nets_hint_timed_dev(d_field, grid, isovalue, hint, queue_max, device, stream, d_out_xyz, vertex_capacity, d_out_tri,
+                                            triangle_capacity, out_nvertices, out_ntriangles, opt_out_seed_cube, nullptr, nullptr);
+}
+
+int pcpx_surface_nets_hint(const float* field, const pcpx_grid3d* grid, float isovalue, const float hint[3], uint64_t queue_max, int device,
+                           float* out_xyz, uint64_t vertex_capacity, uint32_t* out_tri, uint64_t triangle_capacity, uint64_t* out_nvertices,
+                           uint64_t* out_ntriangles, uint64_t* opt_out_seed_cube)
+{
+    if (opt_out_seed_cube) *opt_out_seed_cube = UINT64_MAX;
+    if (!grid || !hint || !out_nvertices || !out_ntriangles) return PCPX_ERR_INVALID;
+    *out_nvertices = *out_ntriangles = 0;
+    if (!std::isfinite(hint[0]) || !std::isfinite(hint[1]) || !std::isfinite(hint[2])) return PCPX_ERR_INVALID;
+    if (grid->sx == 0 || grid->sy == 0 || grid->sz == 0) return PCPX_OK;
+    if (!field) return PCPX_ERR_INVALID;
+    const int valid = check_surface_grid(*grid);  // (before the field is read)
+    if (valid != PCPX_OK) return valid;
+    return on_shared(device, "pcpx_surface_nets_hint", [&](DeviceShared& sh) -> int {
+        PooledStream ps;
+        PCPX_HIP(pooled_stream_get(&ps.s));
+        const hipStream_t s = ps.s;
+        const u64 corners = (grid->sx + 1) * (grid->sy + 1) * (grid->sz + 1);
+        DevBuf df(sh.pool), dv(sh.pool), dt(sh.pool);
+        int r;
+        if ((r = df.alloc(corners * sizeof(float))) != PCPX_OK) return r;
+        const u64 vcap = out_xyz ? vertex_capacity : 0, tcap = out_tri ? triangle_capacity : 0;
+        if ((vcap > 0 && (r = dv.alloc(vcap * 3 * sizeof(float))) != PCPX_OK) || (tcap > 0 && (r = dt.alloc(tcap * 3 * sizeof(u32))) != PCPX_OK))
+            return r;
+        if ((r = upload_pageable(df.p, field, corners * sizeof(float), s)) != PCPX_OK) return r;
+        u64 seed = UINT64_MAX;
+        r = surface_nets_hint_device(df.as<float>(), *grid, isovalue, hint, queue_max, s, sh.pool, dv.as<float>(), vcap, dt.as<u32>(), tcap,
+                                     out_nvertices, out_ntriangles, &seed, nullptr, nullptr);
+        if (opt_out_seed_cube) *opt_out_seed_cube = seed;
+        if (r != PCPX_OK) return r;
+        if (*out_nvertices) PCPX_HIP(hipMemcpyAsync(out_xyz, dv.p, *out_nvertices * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (*out_ntriangles) PCPX_HIP(hipMemcpyAsync(out_tri, dt.p, *out_ntriangles * 3 * sizeof(u32), hipMemcpyDeviceToHost, s));
+        PCPX_HIP(hipStreamSynchronize(s));
+        return PCPX_OK;
+    });
+}
+
+int pcpx_surface_nets_search_order(uint64_t queue_max, int32_t* out_offsets, uint64_t capacity, uint64_t* out_count, int* out_bounded)
+{
+    if (!out_count || !out_bounded) return PCPX_ERR_INVALID;
+    *out_count = 0;
+    *out_bounded = 0;
+    return on_host("pcpx_surface_nets_search_order",
+                   [&]() -> int { return surface_nets_search_order(queue_max, out_offsets, capacity, out_count, out_bounded); });
 }
 
 int pcpx_tangent_plane_sdf_dev(pcpx_index* h, const float* d_centroids, const float* d_normals, const pcpx_grid3d* grid, float eps,

@@ -266,6 +266,22 @@ class Index:
         check(self._lib.pcpx_mean_knn_distance_self(self._h, k, eps, _vp(out)))
         return out
 
+    def surface_hint(self, xyz, k, eps=1e-5):
+        """The hint of the example's `graph` meshing variant (examples/tangent_plane_surface_reconstruction.cpp:393-445) for
+        surface_nets_from_hint: the densest point -- the smallest mean distance to its k nearest neighbours, the first index on
+        a tie (std::min_element) -- and the centroid of its k nearest neighbours, summed from zero in row order.  xyz: the
+        indexed points, in input order."""
+        xyz = _f32(xyz, 3)
+        if len(xyz) != self.n_in:
+            raise ValueError("xyz must be the %d indexed points" % self.n_in)
+        mean = self.mean_knn_distance_self(k, eps)
+        densest = int(np.argmin(np.where(np.isnan(mean), np.float32(np.inf), mean)))
+        idx, cnt = self.knn(xyz[densest:densest + 1], k, eps)
+        acc = np.zeros(3, np.float32)
+        for j in idx[0, :int(cnt[0])]:
+            acc = (acc + xyz[j]).astype(np.float32)
+        return (acc / np.float32(cnt[0])).astype(np.float32)
+
     def normals_from_knn(self, nbr, cnt, want_evals=False):
         nbr = np.ascontiguousarray(nbr, np.uint32)
         cnt = np.ascontiguousarray(cnt, np.uint32)

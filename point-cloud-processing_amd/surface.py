@@ -1,6 +1,7 @@
 """Surface reconstruction over the C ABI: pcp::common::regular_grid3d_t / regular_grid_containing
 (include/pcp/common/regular_grid3d.hpp) and pcp::algorithm::isosurface::surface_nets
-(include/pcp/algorithm/surface_nets.hpp:357-650, the overload that marches over the whole grid).
+(include/pcp/algorithm/surface_nets.hpp:357-650, the overload that marches over the whole grid; :653-1119, the overload with a
+hint point, is surface_nets_from_hint).
 
 A field holds one value per grid corner, corner (i, j, k) at i + j*(sx+1) + k*(sx+1)*(sy+1): a numpy array of shape
 (sz+1, sy+1, sx+1) or anything of that many float32 values.  Meshes are (vertices (V, 3) float32, triangles (T, 3) uint32).
@@ -98,6 +99,87 @@ def surface_nets(field, grid, isovalue=0.0, device=0):
         check(lib.pcpx_surface_nets(f.ctypes.data_as(C.c_void_p), C.byref(g), float(isovalue), device, v.ctypes.data_as(C.c_void_p), nv.value,
                                     t.ctypes.data_as(C.c_void_p), nt.value, C.byref(nv), C.byref(nt)))
     return v, t
+
+
+def surface_nets_from_hint(field, grid, hint, isovalue=0.0, queue_max=32768, with_seed=False, device=0):
+    """Surface nets of the connected component that the reference's search from `hint` reaches first (pcpx_surface_nets_hint,
+    DESIGN.md section 15): the whole-grid mesh restricted to that component, vertices in ascending cube index.  queue_max: the
+    reference's breadth_first_search_queue_max_size (0: no bound).  with_seed: also the seed's linear cube index, or None
+    where the search fell back to the whole grid (or found no active cube)."""
+    lib = _capi.load()
+    g = _grid_of(grid)
+    h = np.ascontiguousarray(hint, np.float32).reshape(3)
+    hp = h.ctypes.data_as(_capi.f32p)
+    nv, nt, seed = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    if _is_device_tensor(field):
+        import torch
+        if field.dtype != torch.float32 or not field.is_contiguous() or field.numel() != _corners(g):
+            raise ValueError("field must be a contiguous float32 tensor of (sx+1)(sy+1)(sz+1) values")
+        dev = field.device.index or 0
+        stream = torch.cuda.current_stream(field.device).cuda_stream
+
+        def call(v, t):
+            return lib.pcpx_surface_nets_hint_dev(C.c_void_p(field.data_ptr()), C.byref(g), float(isovalue), hp, int(queue_max), dev,
+                                                  C.c_void_p(stream), None if v is None else C.c_void_p(v.data_ptr()),
+                                                  0 if v is None else len(v), None if t is None else C.c_void_p(t.data_ptr()),
+                                                  0 if t is None else len(t), C.byref(nv), C.byref(nt), C.byref(seed))
+        st = call(None, None)
+        if st not in (_capi.PCPX_OK, _capi.PCPX_ERR_CAPACITY):
+            check(st)
+        v = torch.empty((nv.value, 3), dtype=torch.float32, device=field.device)
+        t = torch.empty((nt.value, 3), dtype=torch.int32, device=field.device)  # (uint32 vertex indices)
+        if st == _capi.PCPX_ERR_CAPACITY:
+            check(call(v, t))
+    else:
+        f = np.ascontiguousarray(field, np.float32).ravel()
+        if f.size != _corners(g) and min(g.sx, g.sy, g.sz) > 0:
+            raise ValueError("field has %d values, the grid %d corners" % (f.size, _corners(g)))
+
+        def call(v, t):
+            return lib.pcpx_surface_nets_hint(f.ctypes.data_as(C.c_void_p), C.byref(g), float(isovalue), hp, int(queue_max), device,
+                                              None if v is None else v.ctypes.data_as(C.c_void_p), 0 if v is None else len(v),
+                                              None if t is None else t.ctypes.data_as(C.c_void_p), 0 if t is None else len(t),
+                                              C.byref(nv), C.byref(nt), C.byref(seed))
+        st = call(None, None)
+        if st not in (_capi.PCPX_OK, _capi.PCPX_ERR_CAPACITY):
+            check(st)
+        v = np.empty((nv.value, 3), np.float32)
+        t = np.empty((nt.value, 3), np.uint32)
+        if st == _capi.PCPX_ERR_CAPACITY:
+            check(call(v, t))
+    if not with_seed:
+        return v, t
+    return v, t, None if seed.value == _capi.UINT64_MAX else int(seed.value)
+
+
+def surface_nets_hint_raw(field, grid, hint, isovalue, queue_max, vertex_capacity, triangle_capacity, device=0):
+    """pcpx_surface_nets_hint with explicit capacities: (status, V, T, vertices, triangles, seed), the arrays sized by the
+    capacities."""
+    lib = _capi.load()
+    g = _grid_of(grid)
+    f = np.ascontiguousarray(field, np.float32).ravel()
+    h = np.ascontiguousarray(hint, np.float32).reshape(3)
+    v = np.zeros((vertex_capacity, 3), np.float32)
+    t = np.zeros((triangle_capacity, 3), np.uint32)
+    nv, nt, seed = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    st = lib.pcpx_surface_nets_hint(f.ctypes.data_as(C.c_void_p), C.byref(g), float(isovalue), h.ctypes.data_as(_capi.f32p), int(queue_max),
+                                    device, v.ctypes.data_as(C.c_void_p), vertex_capacity, t.ctypes.data_as(C.c_void_p), triangle_capacity,
+                                    C.byref(nv), C.byref(nt), C.byref(seed))
+    return st, int(nv.value), int(nt.value), v, t, int(seed.value)
+
+
+def search_order(queue_max):
+    """The hint search's table (pcpx_surface_nets_search_order): ((N, 3) int32 offsets from the hint cube in the reference's
+    first-pop order, bounded)."""
+    lib = _capi.load()
+    n, b = C.c_uint64(0), C.c_int(0)
+    st = lib.pcpx_surface_nets_search_order(int(queue_max), None, 0, C.byref(n), C.byref(b))
+    if st not in (_capi.PCPX_OK, _capi.PCPX_ERR_CAPACITY):
+        check(st)
+    out = np.zeros((n.value, 3), np.int32)
+    if n.value:
+        check(lib.pcpx_surface_nets_search_order(int(queue_max), out.ctypes.data_as(C.c_void_p), n.value, C.byref(n), C.byref(b)))
+    return out, bool(b.value)
 
 
 def surface_nets_raw(field, grid, isovalue, vertex_capacity, triangle_capacity, device=0):
