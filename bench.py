@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- kNN + normal-estimation throughput of the pcpx hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 Workload (config.workload): the north-star target configuration of BASELINE.json -- a 10 M-point
@@ -13,8 +13,12 @@ One STEP = one pass of the query hot path over the whole cloud with the index re
 k_knn launch (k nearest neighbours of every point, rows written to HBM, with the 3x3 scatter matrix +
 eigen-solve of every point's neighbourhood fused in, normals written to HBM).  The index build is timed
 separately and reported in "extra" (the reference's own benchmarks also build once and time queries:
-benchmark/spatial_data_structures_benchmark.cpp:243-264); "extra.value_incl_build" gives the rate with a
-rebuild inside every step.
+benchmark/spatial_data_structures_benchmark.cpp:243-264); with --full, "extra.value_incl_build" gives the
+rate with a rebuild inside every step.
+
+A plain run does only what the headline line needs: set-up, the warm-up and timed steps, --dump-outputs,
+and the line (roofline and per-kernel averages of the timed steps included).  Everything else it can
+measure is behind --full (see below).
 
 Other workloads (--workload; never the driver's default): clustered_10m_k15 (configs[3]'s cloud) and
 uniform_50m_k32_stream (configs[4]: every step re-jitters the cloud, rebuilds the index and answers
@@ -28,11 +32,14 @@ with RCCL (24 B per rank, the only collective), and every rank builds a RANK-LOC
 index, csrc/pcpx_shard.hip) and answers that shard.  Total work is fixed => "strong".
 PCPX_BENCH_REPLICATED=1 makes every rank index the whole cloud instead (rounds 1-3).
 
-The default single-GPU run also reports BASELINE.json's other configs under extra.configs -- each
-measured in a child process of its own, so that the headline kernel's per-launch average stays that of the
-headline workload -- with, for the multi-GPU configs, one rank's share of an 8-rank step timed on this GPU
-for every rank in turn (a PROJECTION of the 8-GPU step, labelled as such), the reference's own benchmark
-shapes (single-query kNN / range latency) and one end-to-end figure through the host-pointer ABI.
+--full adds, after the timed steps, the side measurements on the same index (rebuild, radius counts and
+lists, the step with rows at curve positions), the host-pointer ABI rates with the normals' float64 check,
+one rank's share of an 8-rank step of the workload, and the CPU baseline.  A single-GPU --full run of the
+default workload also reports BASELINE.json's other configs under extra.configs -- each measured in a
+child process of its own, so that the headline kernel's per-launch average stays that of the headline
+workload -- with, for the multi-GPU configs, one rank's share of an 8-rank step timed on this GPU for every
+rank in turn (a PROJECTION of the 8-GPU step, labelled as such), the reference's own benchmark shapes
+(single-query kNN / range latency) and one end-to-end figure through the host-pointer ABI.
 """
 import argparse
 import importlib
@@ -550,13 +557,18 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="uniform_10m_k15", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also measure everything else: the side measurements, extra.configs, the "
+                         "8-rank projection and the CPU baseline (about 35 s more on one MI355X); a plain run does set-up, warm-up, the "
+                         "timed steps and --dump-outputs only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--rows-at-curve-positions", action="store_true",
                     help="the step writes rows and normals at curve positions (pcpx_knn_self_curve_order_dev) instead of input indices: "
                          "for counter passes of that form; the default line is the input-order form")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the side measurements (rebuild, range count, host-pointer ABI rates, normal evidence): the "
-                         "process then launches nothing but the timed steps, which is what the profiling scripts want")
+                    help="with --full: skip the side measurements (rebuild, range count, host-pointer ABI rates, normal evidence, "
+                         "extra.configs, 8-rank projection); a plain run skips them anyway and launches nothing but the timed "
+                         "steps, which is what the profiling scripts want")
     ap.add_argument("--host-api-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--config-child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--end-to-end-child", action="store_true", help=argparse.SUPPRESS)
@@ -565,13 +577,14 @@ def main():
     ap.add_argument("--base-ms", type=float, default=0.0, help=argparse.SUPPRESS)
     ap.add_argument("--base-rebuild-ms", type=float, default=0.0, help=argparse.SUPPRESS)
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip extra.configs (BASELINE.json's other configurations, the latency shapes and the end-to-end figure, each "
-                         "in a child process: about two minutes)")
+                    help="with --full: skip extra.configs (BASELINE.json's other configurations, the latency shapes and the end-to-end "
+                         "figure, each in a child process: about 15 s)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (neighbour rows and counts, normals; a fixed, "
                          "seeded sample of rows when the whole would pass 60 MB) as DIR/<name>.npy; rank 0's buffers when N > 1")
     ap.add_argument("--with-range-consumers", action="store_true",
-                    help="also run tools/filter_bench.py (bilateral filter, WLOP: extras outside the hot path) and report it under extra")
+                    help="with --full: also run tools/filter_bench.py (bilateral filter, WLOP: extras outside the hot path) and report "
+                         "it under extra")
     ap.add_argument("--with-1m", action="store_true",
                     help="also time configs[1] (1 M points, k=15) and report it under extra; off by default so that the "
                          "default command launches k_knn on the headline workload only (its rocprofv3 average then "
@@ -579,6 +592,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.with_range_consumers and not args.full:
+        ap.error("--with-range-consumers is a side measurement: it needs --full")
 
     pkg = importlib.import_module("point-cloud-processing_amd")
     if args.config_child:
@@ -630,7 +645,7 @@ def main():
     if args.gpus != world and rank == 0:
         print("warning: --gpus %d but WORLD_SIZE %d; using WORLD_SIZE" % (args.gpus, world), file=sys.stderr)
 
-    side = not args.no_extra
+    side = args.full and not args.no_extra
     main_res = run_workload(pkg, torch, dist, args.workload, rank, world, args.steps, args.warmup, want_profile=True,
                             rehearse=rehearse, side=side, collective=collective, at_curve_positions=args.rows_at_curve_positions,
                             dump_dir=args.dump_outputs)
@@ -793,7 +808,7 @@ def main():
             extra["one_eighth_shard"] = {"error": repr(e)[:200]}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(main_res["pts"], k)
 
     if world > 1:

@@ -39,7 +39,7 @@ if stats:
     shutil.copyfile(stats[0], os.path.join(dst, tag + "_rocprofv3_kernel_stats.csv"))
     txt = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "rocprof_summary.py"), stats[0]], capture_output=True, text=True).stdout
     open(os.path.join(dst, tag + "_rocprofv3_kernel_stats.txt"), "w").write(
-        "rocprofv3 --kernel-trace --stats -- python3 bench.py   (MI355X, tools/collect_profiles.sh)\n" + txt)
+        "rocprofv3 --kernel-trace --stats -- python3 bench.py --full   (MI355X, tools/collect_profiles.sh)\n" + txt)
 rstats = sorted(glob.glob(os.path.join(src, "trace_rebuild", "**", "*kernel_stats.csv"), recursive=True), key=os.path.getmtime, reverse=True)
 if rstats:
     txt = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "rocprof_summary.py"), rstats[0]], capture_output=True, text=True).stdout

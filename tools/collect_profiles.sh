@@ -17,12 +17,12 @@ echo "pmc done"
 PMC_PASSES=5 bash tools/pmc_passes.sh "$out/pmc_pos" --steps 3 --warmup 1 --rows-at-curve-positions > "$out/pmc_pos.txt" 2>&1 || { echo "pmc (curve positions) failed"; tail -5 "$out/pmc_pos.txt"; }
 # (the HBM traffic file bench.py quotes under roofline.traffic is made from these passes before the bench line is taken)
 python3 tools/collect_profiles.py "$tag" > /dev/null 2>&1
-# 2. the default command (python3 bench.py) under rocprofv3 --kernel-trace --stats
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- python3 bench.py > "$out/bench_under_rocprofv3.json" 2> "$out/trace.err" || { echo "trace failed"; tail -5 "$out/trace.err"; }
+# 2. the full command (python3 bench.py --full) under rocprofv3 --kernel-trace --stats
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- python3 bench.py --full > "$out/bench_under_rocprofv3.json" 2> "$out/trace.err" || { echo "trace failed"; tail -5 "$out/trace.err"; }
 echo "trace done"
 python3 tools/collect_profiles.py "$tag" > /dev/null 2>&1  # (the shader clock of the issue figure comes from this trace)
-# 3. the bench line (default workload, CPU baseline included; --with-1m adds the configs[1] side figure)
-timeout -k 10 400 python3 bench.py --with-1m > "$out/bench.json" 2> "$out/bench.err" || { echo "bench failed"; tail -5 "$out/bench.err"; }
+# 3. the bench line with everything --full adds (default workload, CPU baseline included; --with-1m adds the configs[1] side figure)
+timeout -k 10 400 python3 bench.py --full --with-1m > "$out/bench.json" 2> "$out/bench.err" || { echo "bench failed"; tail -5 "$out/bench.err"; }
 echo "bench done"
 # 4. traversal statistics + per-phase clocks (diagnostic build of the kernel)
 timeout -k 10 200 python3 tools/knn_stats.py 1e7 uniform 15 > "$out/stats_uniform.json" 2>> "$out/stats.err" &&
@@ -31,9 +31,9 @@ echo "stats done"
 fi
 if [ "$part" = all ] || [ "$part" = knn ] || [ "$part" = knn2 ]; then
 # 5. other workloads: configs[3]'s cloud on one GPU, configs[4] streaming
-timeout -k 10 300 python3 bench.py --workload clustered_10m_k15 --no-cpu-baseline > "$out/bench_clustered_10m_k15.json" 2>> "$out/bench.err" || echo "clustered failed"
+timeout -k 10 300 python3 bench.py --full --workload clustered_10m_k15 --no-cpu-baseline > "$out/bench_clustered_10m_k15.json" 2>> "$out/bench.err" || echo "clustered failed"
 timeout -k 10 300 python3 bench.py --workload uniform_10m_k8 --no-cpu-baseline --no-extra > "$out/bench_uniform_10m_k8.json" 2>> "$out/bench.err" || echo "k8 failed"
-timeout -k 10 500 python3 bench.py --workload uniform_50m_k32_stream --no-cpu-baseline --steps 5 > "$out/bench_c5_50m_k32_stream.json" 2>> "$out/bench.err" || echo "c5 failed"
+timeout -k 10 500 python3 bench.py --full --workload uniform_50m_k32_stream --no-cpu-baseline --steps 5 > "$out/bench_c5_50m_k32_stream.json" 2>> "$out/bench.err" || echo "c5 failed"
 echo "workloads done"
 timeout -k 10 300 python3 tools/shard_rate.py > "$out/shard_rate.json" 2>> "$out/bench.err" || echo "shard failed"
 timeout -k 10 300 python3 tools/shard_rate.py clustered 1e7 15 > "$out/shard_rate_clustered.json" 2>> "$out/bench.err" || echo "shard clustered failed"
