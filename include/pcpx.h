@@ -152,19 +152,21 @@ int pcpx_knn_self(pcpx_index* idx, uint32_t k, float eps, uint32_t* out_idx, uin
 /* Arbitrary query points. */
 int pcpx_knn_batch(pcpx_index* idx, const float* q_xyz, uint64_t nq, uint32_t k, float eps,
                    uint32_t* out_idx, uint32_t* out_count, float* out_d2);
-/* Device-pointer form.  Only curve-sorted positions [sorted_first, sorted_first+sorted_count) are
- * processed (rows of the other points are left untouched) -- the per-rank query shard of the
- * multi-GPU path; pass 0, UINT64_MAX for all.  sorted_first must be a multiple of 64. */
+/* Device-pointer form.  Exactly the curve-sorted positions [sorted_first, sorted_first+sorted_count) are
+ * processed (rows of the other points are left untouched, also where the slice ends inside a group of 64)
+ * -- the per-rank query shard of the multi-GPU path; pass 0, UINT64_MAX for all.  sorted_first must be a
+ * multiple of 64. */
 int pcpx_knn_self_dev(pcpx_index* idx, uint32_t k, float eps, uint64_t sorted_first, uint64_t sorted_count,
                       uint32_t* d_out_idx, uint32_t* d_out_count, float* d_out_d2);
 int pcpx_knn_batch_dev(pcpx_index* idx, const float* d_q_xyz, uint64_t nq, uint32_t k, float eps,
                        uint32_t* d_out_idx, uint32_t* d_out_count, float* d_out_d2);
 /* pcpx_knn_self_dev with `row_stride` entries between the rows of d_out_idx / d_out_d2 (0: k; otherwise >= k, k <= 32; entries
- * k .. row_stride of a row are 0xFFFFFFFF / +inf).  The reference returns one std::vector per query
- * (include/pcp/octree/linked_octree.hpp:245-254), so the row pitch is this library's to choose: with row_stride = 16 (k = 15 or 16;
- * 8 for k = 7, 8; 32 for k = 31, 32) and outputs aligned to 16 bytes a row is ONE aligned 64-byte piece, written with 16-byte
- * stores.  Packed 60-byte rows scattered by input index cost every partial 32-byte sector twice at the memory side (read for
- * ownership + write back): 1.57 GB written per 10 M queries for 0.76 GB of payload (profiles/r04_hbm_traffic.json). */
+ * k .. row_stride of every answered row are 0xFFFFFFFF / +inf, rows of the other points are left untouched).  The reference
+ * returns one std::vector per query (include/pcp/octree/linked_octree.hpp:245-254), so the row pitch is this library's to
+ * choose: with row_stride = 16 (k = 15 or 16; 8 for k = 7, 8; 32 for k = 31, 32) and outputs aligned to 16 bytes a row is ONE
+ * aligned 64-byte piece, written with 16-byte stores.  Packed 60-byte rows scattered by input index cost every partial 32-byte
+ * sector twice at the memory side (read for ownership + write back): 1.57 GB written per 10 M queries for 0.76 GB of payload
+ * (profiles/r04_hbm_traffic.json). */
 int pcpx_knn_self_strided_dev(pcpx_index* idx, uint32_t k, float eps, uint64_t sorted_first, uint64_t sorted_count,
                               uint32_t row_stride, uint32_t* d_out_idx, uint32_t* d_out_count, float* d_out_d2);
 /* Rows by CURVE POSITION, device resident (additive): row p of every output belongs to the p-th point of the curve order,
@@ -182,10 +184,11 @@ int pcpx_index_perm_dev(pcpx_index* idx, uint32_t* d_out_perm, uint32_t* d_opt_o
 /* Count only (what examples/filter_point_cloud_noise_by_density.cpp:81-90 consumes). */
 int pcpx_range_count_self(pcpx_index* idx, float radius, uint32_t* out_count);
 int pcpx_range_count_batch(pcpx_index* idx, const float* q_xyz, uint64_t nq, float radius, uint32_t* out_count);
+/* Slice arguments as pcpx_knn_self_dev: the counts of exactly those positions are written, every other entry is left untouched. */
 int pcpx_range_count_self_dev(pcpx_index* idx, float radius, uint64_t sorted_first, uint64_t sorted_count,
                               uint32_t* d_out_count);
 /* The same with the count of the p-th point of the curve order at d_out_count[p] (positions of the whole cloud's order; rows of
- * a slice are one contiguous piece, written 256 bytes per query group; pcpx_index_perm_dev gives the order).  Additive: the
+ * a slice are one contiguous piece, written 256 bytes per whole query group; pcpx_index_perm_dev gives the order).  Additive: the
  * reference returns results per element (include/pcp/octree/linked_octree.hpp:264-276); a consumer that reduces the counts
  * (examples/filter_point_cloud_noise_by_density.cpp:81-90 thresholds them) does not care about their order. */
 int pcpx_range_count_self_curve_order_dev(pcpx_index* idx, float radius, uint64_t sorted_first, uint64_t sorted_count,

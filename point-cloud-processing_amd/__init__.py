@@ -9,10 +9,10 @@ from .simplify import hierarchy_simplification, hierarchy_simplification_dev  # 
 from .surface import regular_grid_containing, surface_nets, surface_nets_from_hint  # noqa: F401
 from .filters import bilateral_filter_normals, bilateral_filter_points, wlop  # noqa: F401
 from .index import (Index, KdTreeK, LinkedKdTree, LinkedOctree, PcpxError, bounding_box, device_count,  # noqa: F401
-                    estimate_normal, estimate_normals, propagate_normal_orientations, propagate_normal_orientations_dev, shard_range, shard_cuts_by_cost)
+                    estimate_normal, estimate_normals, estimate_normals_batch, propagate_normal_orientations, propagate_normal_orientations_dev, shard_range, shard_cuts_by_cost)
 
 __all__ = ["Index", "LinkedOctree", "LinkedKdTree", "KdTreeK", "PcpxError", "bounding_box", "device_count", "estimate_normal",
-           "estimate_normals", "propagate_normal_orientations", "propagate_normal_orientations_dev", "shard_range", "shard_cuts_by_cost", "ply", "synthetic",
+           "estimate_normals", "estimate_normals_batch", "propagate_normal_orientations", "propagate_normal_orientations_dev", "shard_range", "shard_cuts_by_cost", "ply", "synthetic",
            "bilateral_filter_points", "bilateral_filter_normals", "wlop",
            "Grid3d", "regular_grid_containing", "surface_nets", "surface_nets_from_hint", "surface",
            "hierarchy_simplification", "hierarchy_simplification_dev", "simplify"]

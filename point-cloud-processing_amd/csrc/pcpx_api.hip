@@ -10,14 +10,21 @@
 namespace pcpx {
 namespace {
 
-void slice_to_groups(const Index& ix, u64 sorted_first, u64 sorted_count, u64& gfirst, u64& gcount)
+// A slice [sorted_first, sorted_first + sorted_count) of the curve order, clamped to the cloud: exactly the positions [lo, hi) are
+// answered (the lanes of its first and last query groups outside them idle), and gc groups from group gf hold them
+struct Slice {
+    u64 lo, hi, gf, gc;
+};
+Slice slice_of(const Index& ix, u64 sorted_first, u64 sorted_count)
 {
-    u64 n = ix.n;
-    if (sorted_first > n) sorted_first = n;
-    u64 end = (sorted_count > n - sorted_first) ? n : sorted_first + sorted_count;
-    gfirst = sorted_first / GROUP;
-    u64 gend = (end + GROUP - 1) / GROUP;
-    gcount = gend > gfirst ? gend - gfirst : 0;
+    const u64 n = ix.n;
+    Slice s;
+    s.lo = sorted_first < n ? sorted_first : n;
+    s.hi = sorted_count > n - s.lo ? n : s.lo + sorted_count;
+    s.gf = s.lo / GROUP;
+    const u64 gend = (s.hi + GROUP - 1) / GROUP;
+    s.gc = gend > s.gf ? gend - s.gf : 0;
+    return s;
 }
 
 // The second half of a batch range search with host outputs: the counts of the nq ranges (device) to offsets (host), the capacity
@@ -92,23 +99,24 @@ int ensure_gather_arrays(Index& ix, size_t bytes_per_position = sizeof(float4))
     return PCPX_OK;
 }
 
-// Sphere counts of the query groups [gf, gf + gc) of a whole-cloud handle, BY INPUT INDEX.  Switch "gather_counts" (off): the kernel
+// Sphere counts of the curve positions of slice `sl` of a whole-cloud handle, BY INPUT INDEX.  Switch "gather_counts" (off): the kernel
 // leaves the count of curve position p at [p] of a scratch array (256 contiguous bytes per query group) and k_gather_u32 takes them
 // to input order with coalesced writes.  Written straight to input index perm[p] they are 4 bytes per 32-byte sector, read for
 // ownership and written back (320 MB at the memory side for 40 MB of counts) -- and still faster than the permute's ten million
 // random reads (measured, round 5: 1.92-2.08 ms straight, 2.13 through the permute).
-int range_count_self_rows(Index& ix, u64 gf, u64 gc, float radius, u32* d_out_count)
+int range_count_self_rows(Index& ix, const Slice& sl, float radius, u32* d_out_count)
 {
     QueryView qv = self_view(ix);
-    if (ix.tuning.gather_counts && gc > 0 && ensure_gather_arrays(ix, sizeof(u32)) == PCPX_OK) {
+    qv.pos_lo = static_cast<u32>(sl.lo);
+    qv.pos_hi = static_cast<u32>(sl.hi);
+    if (ix.tuning.gather_counts && sl.gc > 0 && ensure_gather_arrays(ix, sizeof(u32)) == PCPX_OK) {
         u32* at_position = reinterpret_cast<u32*>(ix.d_nc4);  // (n + 64 float4: room for n counts)
         qv.by_position = 1;
-        int st = launch_range_count(ix, qv, true, gf, gc, radius, nullptr, at_position);
+        int st = launch_range_count(ix, qv, true, sl.gf, sl.gc, radius, nullptr, at_position);
         if (st != PCPX_OK) return st;
-        const u64 lo = gf * GROUP, hi = (gf + gc) * GROUP < ix.n ? (gf + gc) * GROUP : ix.n;
-        return launch_gather_u32(ix, at_position, ix.d_pos_of, ix.n_in, static_cast<u32>(lo), static_cast<u32>(hi), d_out_count);
+        return launch_gather_u32(ix, at_position, ix.d_pos_of, ix.n_in, static_cast<u32>(sl.lo), static_cast<u32>(sl.hi), d_out_count);
     }
-    return launch_range_count(ix, qv, true, gf, gc, radius, nullptr, d_out_count);
+    return launch_range_count(ix, qv, true, sl.gf, sl.gc, radius, nullptr, d_out_count);
 }
 
 int check_row_stride(const char* what, u32 row_stride, u32 k)
@@ -136,8 +144,10 @@ int knn_self_dev(Index* ix, const char* what, u32 k, float eps, u64 sorted_first
         }
         return shard_knn_self(*ix, sorted_first, sorted_count, k, eps, o);
     }
-    u64 gf, gc;
-    slice_to_groups(*ix, sorted_first, sorted_count, gf, gc);
+    const Slice sl = slice_of(*ix, sorted_first, sorted_count);
+    const u64 gf = sl.gf, gc = sl.gc;
+    o.pos_lo = static_cast<u32>(sl.lo);
+    o.pos_hi = static_cast<u32>(sl.hi);
     // Input-order normals (+ counts) by the gather-form permute: the kernel leaves {normal, count} at the query's CURVE position (one
     // contiguous kilobyte per wave) and k_gather_nc4 takes them to input order with coalesced writes.  Written straight to row
     // perm[p] they are 12 + 4 bytes scattered over the whole output: every store instruction touches 64 lines, and every partial
@@ -149,9 +159,7 @@ int knn_self_dev(Index* ix, const char* what, u32 k, float eps, u64 sorted_first
         o.normals = nullptr;
         o.cnt = nullptr;
         if ((st = launch_knn(*ix, self_view(*ix), true, gf, gc, k, eps, o)) != PCPX_OK) return st;
-        // (what the launch answered: whole groups -- a slice that ends inside a group is answered to that group's end)
-        const u64 lo = gf * GROUP, hi = (gf + gc) * GROUP < ix->n ? (gf + gc) * GROUP : ix->n;
-        return launch_gather_nc4(*ix, ix->d_nc4, ix->d_pos_of, ix->n_in, static_cast<u32>(lo), static_cast<u32>(hi), d_out_normals, d_opt_out_count);
+        return launch_gather_nc4(*ix, ix->d_nc4, ix->d_pos_of, ix->n_in, o.pos_lo, o.pos_hi, d_out_normals, d_opt_out_count);
     }
     if (k > 32 && (!o.idx || !o.cnt)) {  // the multi-pass path materialises rows: keep them in index scratch
         size_t need_idx = (static_cast<size_t>(ix->n_in) * k * sizeof(u32) + 255) / 256 * 256;
@@ -552,9 +560,7 @@ int pcpx_range_count_self_dev(pcpx_index* h, float radius, uint64_t sorted_first
     if (!d_out_count) return PCPX_ERR_INVALID;
     if ((st = check_slice("pcpx_range_count_self_dev", sorted_first)) != PCPX_OK) return st;
     if (ix->shard.on) return shard_range_count_self(*ix, radius, sorted_first, sorted_count, d_out_count);
-    u64 gf, gc;
-    slice_to_groups(*ix, sorted_first, sorted_count, gf, gc);
-    return range_count_self_rows(*ix, gf, gc, radius, d_out_count);
+    return range_count_self_rows(*ix, slice_of(*ix, sorted_first, sorted_count), radius, d_out_count);
     });
 }
 
@@ -568,11 +574,12 @@ int pcpx_range_count_self_curve_order_dev(pcpx_index* h, float radius, uint64_t 
     if (!d_out_count) return PCPX_ERR_INVALID;
     if ((st = check_slice("pcpx_range_count_self_curve_order_dev", sorted_first)) != PCPX_OK) return st;
     if (ix->shard.on) return shard_range_count_self(*ix, radius, sorted_first, sorted_count, d_out_count, true);
-    u64 gf, gc;
-    slice_to_groups(*ix, sorted_first, sorted_count, gf, gc);
+    const Slice sl = slice_of(*ix, sorted_first, sorted_count);
     QueryView qv = self_view(*ix);
     qv.by_position = 1;
-    return launch_range_count(*ix, qv, true, gf, gc, radius, nullptr, d_out_count);
+    qv.pos_lo = static_cast<u32>(sl.lo);
+    qv.pos_hi = static_cast<u32>(sl.hi);
+    return launch_range_count(*ix, qv, true, sl.gf, sl.gc, radius, nullptr, d_out_count);
     });
 }
 
@@ -595,8 +602,8 @@ int pcpx_range_lists_self_dev(pcpx_index* h, float radius, uint64_t* d_out_offse
     u32* d_cnt = static_cast<u32*>(ix->d_scratch);
     u64* d_sums = reinterpret_cast<u64*>(static_cast<char*>(ix->d_scratch) + cnt_bytes);
     if (ix->n != ix->n_in) PCPX_HIP(hipMemsetAsync(d_cnt, 0, rows * sizeof(u32), ix->stream));  // (points outside the grid: empty lists)
-    const u64 groups = (ix->n + GROUP - 1) / GROUP;
-    if ((st = range_count_self_rows(*ix, 0, groups, radius, d_cnt)) != PCPX_OK) return st;
+    const Slice all = slice_of(*ix, 0, UINT64_MAX);
+    if ((st = range_count_self_rows(*ix, all, radius, d_cnt)) != PCPX_OK) return st;
     if ((st = launch_range_offsets(*ix, d_cnt, rows, d_sums, d_out_offsets)) != PCPX_OK) return st;
     u64 total = 0;
     PCPX_HIP(hipMemcpyAsync(&total, d_out_offsets + rows, sizeof(u64), hipMemcpyDeviceToHost, ix->stream));
@@ -607,7 +614,7 @@ int pcpx_range_lists_self_dev(pcpx_index* h, float radius, uint64_t* d_out_offse
         set_error("pcpx_range_lists_self_dev: need room for %llu indices", static_cast<unsigned long long>(total));
         return PCPX_ERR_CAPACITY;
     }
-    return launch_range_fill_self(*ix, 0, groups, radius, d_out_offsets, d_out_idx);
+    return launch_range_fill_self(*ix, 0, all.gc, radius, d_out_offsets, d_out_idx);
     });
 }
 

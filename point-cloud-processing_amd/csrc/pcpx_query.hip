@@ -1343,6 +1343,13 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
             okmask |= ok ? (1u << s) : 0u;
         }
     }
+    // entries k .. row_stride of the row are padding (include/pcpx.h); whole rows wrote theirs above
+    if (!whole_rows) {
+        for (u32 j = k; j < stride; ++j) {
+            if (o.idx) o.idx[ob + j] = INVALID_ID;
+            if (o.d2 && !STATS) o.d2[ob + j] = __uint_as_float(static_cast<u32>(PAD_KEY >> 32));
+        }
+    }
     if (o.cnt) o.cnt[row] = found;
 
     // ---- fused pcp::algorithm::average_distances_to_neighbors (average_distance_to_neighbors.hpp:52-70):

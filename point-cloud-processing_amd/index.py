@@ -65,6 +65,18 @@ def estimate_normal(points, device=0):
     return out
 
 
+def estimate_normals_batch(points, offsets, device=0):
+    """pcpx_estimate_normals_batch: estimate_normal of every neighbourhood r = points[offsets[r] : offsets[r + 1]] in one launch
+    (nrows + 1 offsets; they must not decrease, and need not start at 0).  Returns nrows x 3 float32."""
+    pts = _f32(points, 3)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    nrows = max(len(off) - 1, 0)
+    out = np.zeros((nrows, 3), np.float32)
+    check(_capi.load().pcpx_estimate_normals_batch(_vp(pts) if len(pts) else None, _vp(off) if len(off) else None, nrows, device,
+                                                   _vp(out) if nrows else None))
+    return out
+
+
 class Index:
     """Owns a pcpx_index handle: the device-resident curve-sorted implicit AABB tree."""
 
@@ -377,6 +389,13 @@ class Index:
         check(self._lib.pcpx_normals_knn_self_dev(self._h, k, eps, first, count, C.c_void_p(d_normals),
                                                   C.c_void_p(d_idx) if d_idx else None,
                                                   C.c_void_p(d_cnt) if d_cnt else None))
+
+    def neighbourhoods_self_dev(self, k, eps, d_normals=None, d_centroids=None, d_meandist=None, first=0, count=_capi.UINT64_MAX):
+        """Per-neighbourhood products of every indexed point's k nearest neighbours, in input order: PCA normals (n x 3),
+        centroids (n x 3), mean Euclidean distances (n; NaN for an empty row).  Any output may be None, not all."""
+        check(self._lib.pcpx_neighbourhoods_self_dev(self._h, k, eps, first, count, C.c_void_p(d_normals) if d_normals else None,
+                                                     C.c_void_p(d_centroids) if d_centroids else None,
+                                                     C.c_void_p(d_meandist) if d_meandist else None))
 
     def range_count_self_dev(self, radius, d_cnt, first=0, count=_capi.UINT64_MAX):
         check(self._lib.pcpx_range_count_self_dev(self._h, radius, first, count, C.c_void_p(d_cnt)))
