@@ -1,7 +1,8 @@
 // pcp::algorithm::average_distances_to_neighbors / average_distance_to_neighbors -- drop-in for
 // include/pcp/algorithm/average_distance_to_neighbors.hpp (:32-73, :89-113): per element, the mean
 // Euclidean distance to the elements its knn_map returns; then the mean of those.  With
-// pcp::gpu::self_knn_map the per-element means come from the fused GPU kernel.
+// pcp::gpu::self_knn_map the per-element means come from the fused GPU kernel, with pcp::gpu::self_range_map / range_map
+// from one launch of the sphere walk's moments form (pcpx_radius.h).
 #ifndef PCP_ALGORITHM_AVERAGE_DISTANCE_TO_NEIGHBORS_HPP
 #define PCP_ALGORITHM_AVERAGE_DISTANCE_TO_NEIGHBORS_HPP
 
@@ -25,7 +26,13 @@ std::vector<ScalarType> average_distances_to_neighbors(RandomAccessIter begin, R
     using knn_type = std::remove_cv_t<std::remove_reference_t<KnnMap>>;
     std::size_t const n = static_cast<std::size_t>(std::distance(begin, end));
     std::vector<ScalarType> mean_distances(n);
-    if constexpr (gpu::is_self_knn_map<knn_type>::value)
+    if constexpr (gpu::is_self_range_map<knn_type>::value || gpu::is_range_map<knn_type>::value)
+    {
+        std::vector<float> m;
+        gpu::range_neighbourhoods(begin, end, knn_map, nullptr, nullptr, &m);
+        for (std::size_t i = 0; i < n; ++i) mean_distances[i] = static_cast<ScalarType>(m[i]);
+    }
+    else if constexpr (gpu::is_self_knn_map<knn_type>::value)
     {
         if (n != knn_map.tree->size())
             throw std::invalid_argument("self_knn_map: the range must be the container's own element sequence");

@@ -6,7 +6,9 @@
 // KnnMap bound to one of this tree's containers: then ONE batched kNN launch answers every element of
 // [begin, end) and ONE launch computes all normals; `op` is applied on the host in input order.
 // If the range is the container's own element sequence, pcp::gpu::self_knn_map_t selects the fused
-// kernel (kNN + PCA normal per point, neighbour lists never leave the GPU).
+// kernel (kNN + PCA normal per point, neighbour lists never leave the GPU).  The sphere-range maps
+// pcp::gpu::self_range_map_t / range_map_t (neighbourhood = range_search(sphere_t{p, r})) take one launch of the sphere walk's
+// moments form instead: normals, centroids and mean distances without any neighbour list (pcpx_radius.h).
 //
 // propagate_normal_orientations (:187-302) keeps the reference's signature and result: a breadth-first
 // propagation over the directed kNN graph.  The visit order decides which parent orients a vertex, so the
@@ -28,6 +30,7 @@
 #include <cmath>
 #include <cstddef>
 #include <iterator>
+#include <limits>
 #include <stdexcept>
 #include <type_traits>
 #include <vector>
@@ -83,6 +86,123 @@ self_knn_map_t<Tree> self_knn_map(Tree const& tree, std::size_t k, float eps = 1
     return self_knn_map_t<Tree>{&tree, k, eps};
 }
 
+// Sphere-range neighbourhood maps: per element, every element within `radius` of its point -- what
+// tree.range_search(sphere_t{p, radius}) returns, so each is a valid KnnMap for any code.  estimate_normals,
+// estimate_tangent_planes and average_distances_to_neighbors recognise them: self_range_map_t becomes ONE launch of the
+// sphere walk's moments form over the whole container (pcpx_range_neighbourhoods_self), range_map_t one batch call
+// (pcpx_range_neighbourhoods_batch); no neighbour list is formed.
+template <class Tree, class QueryPointMap>
+struct range_map_t
+{
+    using element_type = typename Tree::element_type;
+    Tree const* tree;
+    QueryPointMap query_point;
+    float radius;
+
+    std::vector<element_type> operator()(element_type const& e) const
+    {
+        auto const p = query_point(e);
+        float const q[3] = {static_cast<float>(p.x()), static_cast<float>(p.y()), static_cast<float>(p.z())};
+        std::vector<element_type> out;
+        if (tree->size() == 0) return out;
+        auto const row = tree->index().range_sphere_one(q, radius);
+        out.reserve(row.size());
+        for (std::uint32_t i : row) out.push_back(tree->element(i));
+        return out;
+    }
+};
+template <class Tree, class QueryPointMap>
+range_map_t<Tree, QueryPointMap> range_map(Tree const& tree, QueryPointMap query_point, float radius)
+{
+    return range_map_t<Tree, QueryPointMap>{&tree, query_point, radius};
+}
+
+// Same, with the promise that the queried range is exactly the container's elements in insertion order.
+template <class Tree>
+struct self_range_map_t
+{
+    using element_type = typename Tree::element_type;
+    Tree const* tree;
+    float radius;
+
+    std::vector<element_type> operator()(element_type const& e) const { return tree->range_search_of(e, radius); }
+};
+template <class Tree>
+self_range_map_t<Tree> self_range_map(Tree const& tree, float radius)
+{
+    return self_range_map_t<Tree>{&tree, radius};
+}
+
+template <class T>
+struct is_range_map : std::false_type
+{
+};
+template <class Tree, class Q>
+struct is_range_map<range_map_t<Tree, Q>> : std::true_type
+{
+};
+template <class T>
+struct is_self_range_map : std::false_type
+{
+};
+template <class Tree>
+struct is_self_range_map<self_range_map_t<Tree>> : std::true_type
+{
+};
+
+// the query points of [begin, end) through a range_map_t's query_point, as n x 3 floats
+template <class ForwardIter, class RangeMap>
+std::vector<float> query_points_of(ForwardIter begin, ForwardIter end, RangeMap const& m)
+{
+    std::vector<float> q;
+    for (; begin != end; ++begin)
+    {
+        auto const p = m.query_point(*begin);
+        q.push_back(static_cast<float>(p.x()));
+        q.push_back(static_cast<float>(p.y()));
+        q.push_back(static_cast<float>(p.z()));
+    }
+    return q;
+}
+
+// The per-neighbourhood products of a range map over [begin, end): any of normals (n x 3), centroids (n x 3), mean distances
+// (n) -- a null pointer is not computed
+template <class ForwardIter, class Map>
+void range_neighbourhoods(ForwardIter begin, ForwardIter end, Map const& m, std::vector<float>* normals, std::vector<float>* centroids,
+                          std::vector<float>* mean_dist)
+{
+    using map_type      = std::remove_cv_t<std::remove_reference_t<Map>>;
+    std::size_t const n = static_cast<std::size_t>(std::distance(begin, end));
+    if (normals) normals->assign(3 * n, 0.f);
+    if (centroids) centroids->assign(3 * n, 0.f);
+    if (mean_dist) mean_dist->assign(n, 0.f);
+    float* const dn = normals ? normals->data() : nullptr;
+    float* const dc = centroids ? centroids->data() : nullptr;
+    float* const dm = mean_dist ? mean_dist->data() : nullptr;
+    if (n == 0) return;
+    if (m.tree->size() == 0)  // nothing indexed: every neighbourhood is empty (pcpx_radius.h)
+    {
+        float const nan = std::numeric_limits<float>::quiet_NaN();
+        for (std::size_t i = 0; i < n; ++i)
+        {
+            if (dn) dn[3 * i + 2] = 1.f;
+            if (dc) dc[3 * i] = dc[3 * i + 1] = dc[3 * i + 2] = nan;
+            if (dm) dm[i] = nan;
+        }
+        return;
+    }
+    if constexpr (is_self_range_map<map_type>::value)
+    {
+        if (n != m.tree->size()) throw std::invalid_argument("self_range_map: the range must be the container's own element sequence");
+        m.tree->index().range_neighbourhoods_self(m.radius, n, dn, dc, dm, nullptr);
+    }
+    else
+    {
+        std::vector<float> const q = query_points_of(begin, end, m);
+        m.tree->index().range_neighbourhoods(q.data(), n, m.radius, dn, dc, dm, nullptr);
+    }
+}
+
 template <class T>
 struct is_knn_map : std::false_type
 {
@@ -117,7 +237,14 @@ template <class ForwardIter1, class PointViewMap, class KnnMap, class Normal, cl
 void estimate_normals_impl(ForwardIter1 begin, ForwardIter1 end, PointViewMap const& point_map, KnnMap const& knn, Emit&& emit)
 {
     using knn_type = std::remove_cv_t<std::remove_reference_t<KnnMap>>;
-    if constexpr (gpu::is_self_knn_map<knn_type>::value)
+    if constexpr (gpu::is_self_range_map<knn_type>::value || gpu::is_range_map<knn_type>::value)
+    {
+        std::vector<float> nrm;
+        gpu::range_neighbourhoods(begin, end, knn, &nrm, nullptr, nullptr);
+        std::size_t i = 0;
+        for (; begin != end; ++begin, ++i) emit(*begin, make_normal<Normal>(nrm.data() + 3 * i));
+    }
+    else if constexpr (gpu::is_self_knn_map<knn_type>::value)
     {
         std::size_t const n = static_cast<std::size_t>(std::distance(begin, end));
         if (n != knn.tree->size())

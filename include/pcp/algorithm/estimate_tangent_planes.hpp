@@ -1,7 +1,8 @@
 // pcp::algorithm::estimate_tangent_planes -- drop-in for include/pcp/algorithm/estimate_tangent_planes.hpp
 // (:50-98 execution-policy overload, :116-176 sequential overload): plane of an element = (centre of
 // geometry of its k neighbours, their PCA normal).  With pcp::gpu::self_knn_map the whole loop is the fused
-// GPU kernel (pcpx_tangent_planes_knn_self); any other KnnMap takes the reference's per-element path.
+// GPU kernel (pcpx_tangent_planes_knn_self), with pcp::gpu::self_range_map / range_map one launch of the sphere walk's moments
+// form (pcpx_radius.h); any other KnnMap takes the reference's per-element path.
 #ifndef PCP_ALGORITHM_ESTIMATE_TANGENT_PLANES_HPP
 #define PCP_ALGORITHM_ESTIMATE_TANGENT_PLANES_HPP
 
@@ -26,7 +27,17 @@ void estimate_tangent_planes_impl(ForwardIter1 begin, ForwardIter1 end, PointMap
     using knn_type    = std::remove_cv_t<std::remove_reference_t<KnnMap>>;
     using point_type  = typename Plane::point_type;
     using normal_type = typename Plane::normal_type;
-    if constexpr (gpu::is_self_knn_map<knn_type>::value)
+    if constexpr (gpu::is_self_range_map<knn_type>::value || gpu::is_range_map<knn_type>::value)
+    {
+        std::vector<float> cen, nrm;
+        gpu::range_neighbourhoods(begin, end, knn, &nrm, &cen, nullptr);
+        std::size_t i = 0;
+        using T = typename point_type::coordinate_type;
+        for (; begin != end; ++begin, ++i)
+            emit(*begin, Plane(point_type{static_cast<T>(cen[3 * i]), static_cast<T>(cen[3 * i + 1]), static_cast<T>(cen[3 * i + 2])},
+                               make_normal<normal_type>(nrm.data() + 3 * i)));
+    }
+    else if constexpr (gpu::is_self_knn_map<knn_type>::value)
     {
         std::size_t const n = static_cast<std::size_t>(std::distance(begin, end));
         if (n != knn.tree->size())

@@ -6,6 +6,7 @@
 #define PCP_GPU_DEVICE_INDEX_HPP
 
 #include "pcpx.h"
+#include "pcpx_radius.h"
 
 #include <array>
 #include <atomic>
@@ -386,6 +387,21 @@ class device_index_t
         std::vector<float> m(static_cast<std::size_t>(rows), 0.f);
         if (rows) check(pcpx_mean_knn_distance_self(h_, k, eps, m.data()), "pcpx_mean_knn_distance_self");
         return m;
+    }
+    // Fixed-radius neighbourhoods (pcpx_radius.h): over every indexed point within `radius` of each indexed point (self) or of each
+    // of n centres, the PCA normal (x 3), the centroid (x 3), the mean distance and the count, in one launch of the sphere walk's
+    // moments form.  Any output pointer may be null (not all); each non-null one holds rows (self) or n rows.
+    void range_neighbourhoods_self(float radius, std::uint64_t rows, float* normals, float* centroids, float* mean_dist,
+                                   std::uint32_t* count) const
+    {
+        if (rows) check(pcpx_range_neighbourhoods_self(h_, radius, normals, centroids, mean_dist, count), "pcpx_range_neighbourhoods_self");
+    }
+    void range_neighbourhoods(float const* centers, std::uint64_t n, float radius, float* normals, float* centroids, float* mean_dist,
+                              std::uint32_t* count) const
+    {
+        if (n)
+            check(pcpx_range_neighbourhoods_batch(h_, centers, nullptr, radius, n, normals, centroids, mean_dist, count),
+                  "pcpx_range_neighbourhoods_batch");
     }
     // propagate_normal_orientations over the index's own kNN graph, all on the GPU; normals: rows x 3, in place
     std::uint64_t orient_normals_self(std::uint32_t k, float eps, std::vector<float>& normals) const

@@ -185,6 +185,17 @@ class basic_linked_kdtree_t
         return nearest_neighbours(e, k, static_cast<coordinate_type>(eps));
     }
 
+    // every element within `radius` of one of the container's own elements (what pcp::gpu::self_range_map_t calls per element)
+    std::vector<element_type> range_search_of(element_type const& e, float radius) const
+    {
+        static_assert(!wide, "sphere ranges on the device index: three coordinates");
+        if (storage_.empty()) return {};
+        auto const c = coordinate_map_(e);
+        float const q[3] = {axis(c, 0), axis(c, 1), axis(c, 2)};
+        auto const idx = index().range_sphere_one(q, radius);
+        return gather(idx.data(), idx.size());
+    }
+
     template <class Range>
     std::vector<element_type> range_search(Range const& range) const
     {

@@ -192,6 +192,16 @@ class basic_linked_octree_t
         return gather(row.data(), row.size());
     }
 
+    // every element within `radius` of one of the container's own elements (range_search(sphere_t{p, radius}) with p its point;
+    // what pcp::gpu::self_range_map_t calls per element)
+    std::vector<element_type> range_search_of(element_type const& e, float radius) const
+    {
+        if (elements_.empty() || !point_of_) return {};
+        auto const q = point_of_(e);
+        auto const idx = index().range_sphere_one(q.data(), radius);
+        return gather(idx.data(), idx.size());
+    }
+
     // every element whose point satisfies range.contains(point)
     template <class Range, class PointViewMap>
     std::vector<element_type> range_search(Range const& range, PointViewMap const& point_view) const

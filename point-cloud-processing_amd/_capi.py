@@ -197,6 +197,16 @@ def _share_hip_runtime_with_torch():
         pass  # fall back to the RUNPATH copy under /opt/rocm
 
 
+# name -> (restype, argtypes); every symbol declared in include/pcpx_radius.h (the fixed-radius neighbourhoods)
+RADIUS_SIGNATURES = {
+    "pcpx_range_neighbourhoods_self_dev": (C.c_int, [C.c_void_p, C.c_float, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p]),
+    "pcpx_range_neighbourhoods_self": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcpx_range_neighbourhoods_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]),
+}
+
+
 def load():
     """Load libpcpx.so; raises if it has not been built (run __graft_entry__.build())."""
     global _lib
@@ -208,7 +218,7 @@ def load():
             "There is no CPU fallback for the pcpx compute path." % LIB_PATH)
     _share_hip_runtime_with_torch()
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(RADIUS_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

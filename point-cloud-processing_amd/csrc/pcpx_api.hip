@@ -1,10 +1,12 @@
-// pcpx_api.hip -- the extern "C" boundary declared in include/pcpx.h.
+// pcpx_api.hip -- the extern "C" boundary declared in include/pcpx.h (and its companion include/pcpx_radius.h).
 // Host-pointer entry points stage through device buffers and are synchronous; *_dev entry points
 // enqueue on the index's stream.  No CPU fallback exists: every compute call needs a HIP device.
 #include "pcpx_internal.h"
+#include "pcpx_radius.h"
 
 #include <algorithm>
 #include <cstring>
+#include <functional>
 #include <vector>
 
 namespace pcpx {
@@ -1209,6 +1211,122 @@ int pcpx_device_download(void* dst, const void* d_src, uint64_t bytes, int devic
     PCPX_HIP(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, static_cast<hipStream_t>(stream)));
     PCPX_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
     return PCPX_OK;
+    });
+}
+
+// ---- fixed-radius neighbourhoods (include/pcpx_radius.h): the moments form of the sphere walk ------------------------------------
+static int check_radius(const char* what, float radius)
+{
+    if (radius >= 0.f) return PCPX_OK;  // (false for NaN)
+    set_error("%s: the radius must be >= 0 (got %g)", what, static_cast<double>(radius));
+    return PCPX_ERR_INVALID;
+}
+
+int pcpx_range_neighbourhoods_self_dev(pcpx_index* h, float radius, uint64_t sorted_first, uint64_t sorted_count,
+                                       float* d_opt_normals, float* d_opt_centroids, float* d_opt_mean_dist, uint32_t* d_opt_count)
+{
+    static const char* what = "pcpx_range_neighbourhoods_self_dev";
+    return on_index(h, what, WHOLE_CLOUD, [&](Index* ix) -> int {
+    int st;
+    if (!d_opt_normals && !d_opt_centroids && !d_opt_mean_dist && !d_opt_count) {
+        set_error("%s: every output is NULL", what);
+        return PCPX_ERR_INVALID;
+    }
+    if ((st = check_radius(what, radius)) != PCPX_OK) return st;
+    if ((st = check_slice(what, sorted_first)) != PCPX_OK) return st;
+    const Slice sl = slice_of(*ix, sorted_first, sorted_count);
+    if (sl.lo == 0 && sl.hi == ix->n && ix->n != ix->n_in) {  // the whole curve order: the rows of the points outside the grid too
+        if ((st = ensure_gather_arrays(*ix, sizeof(u32))) != PCPX_OK) return st;
+        if ((st = launch_range_moments_empty_rows(*ix, ix->d_pos_of, ix->n_in, d_opt_normals, d_opt_centroids, d_opt_mean_dist,
+                                                  d_opt_count)) != PCPX_OK)
+            return st;
+    }
+    QueryView qv = self_view(*ix);
+    qv.pos_lo = static_cast<u32>(sl.lo);
+    qv.pos_hi = static_cast<u32>(sl.hi);
+    return launch_range_moments(*ix, qv, true, sl.gf, sl.gc, radius, nullptr, d_opt_normals, d_opt_centroids, d_opt_mean_dist,
+                                d_opt_count);
+    });
+}
+
+// Host outputs: one device block per asked output, then the copies back
+struct MomentsHost {
+    float* normals;
+    float* centroids;
+    float* mean_dist;
+    uint32_t* count;
+};
+static int moments_to_host(Index* ix, u64 rows, const MomentsHost& out, const std::function<int(float*, float*, float*, u32*)>& run)
+{
+    int st;
+    DevBuf dn(ix->pool), dc(ix->pool), dm(ix->pool), dk(ix->pool);
+    if (out.normals && (st = dn.alloc(rows * 3 * sizeof(float))) != PCPX_OK) return st;
+    if (out.centroids && (st = dc.alloc(rows * 3 * sizeof(float))) != PCPX_OK) return st;
+    if (out.mean_dist && (st = dm.alloc(rows * sizeof(float))) != PCPX_OK) return st;
+    if (out.count && (st = dk.alloc(rows * sizeof(u32))) != PCPX_OK) return st;
+    if ((st = run(dn.as<float>(), dc.as<float>(), dm.as<float>(), dk.as<u32>())) != PCPX_OK) return st;
+    if (out.normals) PCPX_HIP(hipMemcpyAsync(out.normals, dn.p, rows * 3 * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+    if (out.centroids) PCPX_HIP(hipMemcpyAsync(out.centroids, dc.p, rows * 3 * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+    if (out.mean_dist) PCPX_HIP(hipMemcpyAsync(out.mean_dist, dm.p, rows * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+    if (out.count) PCPX_HIP(hipMemcpyAsync(out.count, dk.p, rows * sizeof(u32), hipMemcpyDeviceToHost, ix->stream));
+    PCPX_HIP(hipStreamSynchronize(ix->stream));
+    return PCPX_OK;
+}
+
+int pcpx_range_neighbourhoods_self(pcpx_index* h, float radius, float* opt_normals, float* opt_centroids, float* opt_mean_dist,
+                                   uint32_t* opt_count)
+{
+    static const char* what = "pcpx_range_neighbourhoods_self";
+    return on_index(h, what, WHOLE_CLOUD, [&](Index* ix) -> int {
+    int st;
+    if (!opt_normals && !opt_centroids && !opt_mean_dist && !opt_count) {
+        set_error("%s: every output is NULL", what);
+        return PCPX_ERR_INVALID;
+    }
+    if ((st = check_radius(what, radius)) != PCPX_OK) return st;
+    if (ix->n_in == 0) return PCPX_OK;
+    return moments_to_host(ix, ix->n_in, MomentsHost{opt_normals, opt_centroids, opt_mean_dist, opt_count},
+                           [&](float* dn, float* dc, float* dm, u32* dk) {
+                               return pcpx_range_neighbourhoods_self_dev(h, radius, 0, UINT64_MAX, dn, dc, dm, dk);
+                           });
+    });
+}
+
+int pcpx_range_neighbourhoods_batch(pcpx_index* h, const float* q_xyz, const float* radii, float radius, uint64_t nq,
+                                    float* opt_normals, float* opt_centroids, float* opt_mean_dist, uint32_t* opt_count)
+{
+    static const char* what = "pcpx_range_neighbourhoods_batch";
+    return on_index(h, what, WHOLE_CLOUD, [&](Index* ix) -> int {
+    int st;
+    if (!opt_normals && !opt_centroids && !opt_mean_dist && !opt_count) {
+        set_error("%s: every output is NULL", what);
+        return PCPX_ERR_INVALID;
+    }
+    if (nq > 0 && !q_xyz) return PCPX_ERR_INVALID;
+    if (radii) {
+        for (u64 i = 0; i < nq; ++i)
+            if (!(radii[i] >= 0.f)) {
+                set_error("%s: radius %llu must be >= 0 (got %g)", what, static_cast<unsigned long long>(i), static_cast<double>(radii[i]));
+                return PCPX_ERR_INVALID;
+            }
+    } else if ((st = check_radius(what, radius)) != PCPX_OK) {
+        return st;
+    }
+    if (nq == 0) return PCPX_OK;
+    DevBuf dq(ix->pool), dr(ix->pool);
+    if ((st = dq.alloc(nq * 3 * sizeof(float))) != PCPX_OK) return st;
+    if ((st = upload_pageable(dq.p, q_xyz, nq * 3 * sizeof(float), ix->stream)) != PCPX_OK) return st;
+    if (radii) {
+        if ((st = dr.alloc(nq * sizeof(float))) != PCPX_OK) return st;
+        if ((st = upload_pageable(dr.p, radii, nq * sizeof(float), ix->stream)) != PCPX_OK) return st;
+    }
+    QueryView qv;
+    if ((st = prepare_queries(*ix, dq.as<float>(), nq, qv)) != PCPX_OK) return st;
+    return moments_to_host(ix, nq, MomentsHost{opt_normals, opt_centroids, opt_mean_dist, opt_count},
+                           [&](float* dn, float* dc, float* dm, u32* dk) {
+                               return launch_range_moments(*ix, qv, false, 0, (nq + GROUP - 1) / GROUP, radius, dr.as<float>(), dn, dc,
+                                                           dm, dk);
+                           });
     });
 }
 

@@ -435,6 +435,12 @@ int launch_range_fill(Index& ix, const QueryView& qv, float radius, const float*
 int launch_range_offsets(Index& ix, const u32* d_cnt, u64 n_rows, u64* d_tile_sum, u64* d_offsets);
 int launch_range_fill_self(Index& ix, u64 group_first, u64 group_count, float radius, const u64* d_offsets, u32* d_out_idx);
 int launch_range_one(Index& ix, bool aabb, const float* range, u32 cap, u32* out_idx, u32* out_cnt, u32* done_flag, u32 epoch);
+// the moments form of the sphere walk (normal, centroid, mean distance, count per sphere; any output may be nullptr) and the
+// empty-set values at the rows whose d_pos_of entry is 0xFFFFFFFF (points outside the voxel grid)
+int launch_range_moments(Index& ix, const QueryView& qv, bool self, u64 group_first, u64 group_count, float radius, const float* d_radii,
+                         float* d_normals, float* d_centroids, float* d_mean_dist, u32* d_count);
+int launch_range_moments_empty_rows(Index& ix, const u32* d_pos_of, u64 n_rows, float* d_normals, float* d_centroids, float* d_mean_dist,
+                                    u32* d_count);
 int launch_aabb_count(Index& ix, const float* d_boxes6, u64 nb, u32* d_out_cnt);
 int launch_aabb_fill(Index& ix, const float* d_boxes6, u64 nb, const u64* d_offsets, u32* d_out_idx);
 int launch_normals(Index& ix, const u32* d_nbr, const u32* d_cnt, const u32* d_rowmap, u64 first, u64 count, u32 k,

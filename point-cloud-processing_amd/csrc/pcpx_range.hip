@@ -1,6 +1,7 @@
 // pcpx_range.hip -- radius search kernels (sphere and axis-aligned box ranges) for gfx950: the same wave-uniform
-// walk as the kNN kernel (pcpx_device.h), one lane = one range, count or CSR fill.
+// walk as the kNN kernel (pcpx_device.h), one lane = one range, count, CSR fill or moments (normal, centroid, mean distance).
 #include "pcpx_device.h"
+#include "pcpx_eig3.h"
 
 #ifndef PCPX_RANGE_DIRECT_LEAVES
 #define PCPX_RANGE_DIRECT_LEAVES 1
@@ -35,12 +36,23 @@ namespace {
 // counted eight needing lanes x eight points at a time (count form: packed_leaf below; the fill form keeps the lane-per-range
 // leaf).  10 M counts at r = 0.01: 2.56 ms (round 3 start) -> 2.40 (direct leaves + round 3's point-per-lane form) -> 2.21
 // (round 4: the packed form instead; profiles/experiments/README.md).
-template <bool SELF, bool FILL>
+//
+// MOM (moments form): 1 = per lane the count n, S = sum d and Q = sum d d^T of d = p - q (q: the sphere's
+// centre), then centroid q + S / n and the PCA normal of C = Q - S S^T / n (eig3_smallest, as k_knn and k_normals); 2 = also
+// D = sum |d| for the mean distance D / n.  Lane-per-range leaves only (a packed leaf would need a cross-lane sum of ~11 values).
+struct MomentsOut {
+    float* normals = nullptr;    // rows x 3
+    float* centroids = nullptr;  // rows x 3
+    float* mean_dist = nullptr;  // rows
+    u32* count = nullptr;        // rows
+};
+template <bool SELF, bool FILL, int MOM = 0>
 __device__ __forceinline__ void range_group(const TreeView& t, const QueryView& qv, const u32 g, const float radius,
                                             const float* __restrict__ radii, u32* __restrict__ out_cnt,
                                             const u64* __restrict__ offsets, u32* __restrict__ out_idx, float4* __restrict__ pub,
-                                            const u32 lane)
+                                            const u32 lane, const MomentsOut mo = MomentsOut{})
 {
+    static_assert(MOM == 0 || !FILL, "the moments form lists nothing");
     const u32 p = g * GROUP + lane;
     const u32 nq = SELF ? t.n : qv.nq;
     const bool valid = p < nq && (!SELF || p - qv.pos_lo < qv.pos_hi - qv.pos_lo);  // (self ranges: only the asked positions)
@@ -67,8 +79,24 @@ __device__ __forceinline__ void range_group(const TreeView& t, const QueryView& 
     u32 cnt = 0;
     u64 wpos = (FILL && valid) ? offsets[row] : 0;
     auto need = [&](const NodeBox& b) { return box_d2(b, qx, qy, qz) <= r2; };
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, q00 = 0.f, q10 = 0.f, q11 = 0.f, q20 = 0.f, q21 = 0.f, q22 = 0.f, dsum = 0.f;  // (moments form)
 
     auto leaf_record_points = [&](const Leaf& lf) {
+        if constexpr (MOM != 0) {
+#pragma unroll
+            for (int j = 0; j < LEAF; ++j) {
+                const float dx = lf.x[j] - qx, dy = lf.y[j] - qy, dz = lf.z[j] - qz;
+                const float d2 = sq3(dx, dy, dz);
+                if (d2 <= r2) {  // (a NaN padding point fails)
+                    cnt += 1u;
+                    s0 += dx; s1 += dy; s2 += dz;
+                    q00 += dx * dx; q10 += dy * dx; q11 += dy * dy;
+                    q20 += dz * dx; q21 += dz * dy; q22 += dz * dz;
+                    if (MOM == 2) dsum += sqrtf(d2);
+                }
+            }
+            return;
+        }
         if (!FILL) {
             if (PCPX_RANGE_PRIO_DENSE != PCPX_RANGE_PRIO_BASE) __builtin_amdgcn_s_setprio(PCPX_RANGE_PRIO_DENSE);
             // count: the eight "inside" masks first (a scalar register pair each), then eight add-with-carry -- from
@@ -112,7 +140,7 @@ __device__ __forceinline__ void range_group(const TreeView& t, const QueryView& 
     // and a lane whose point is inside writes the point's index at that place plus the number of set bits below its own in its
     // group's byte of the step's ballot -- the order of a list is the order of the lane-per-range form: walk order, then point
     // order inside a leaf.
-    constexpr bool packed_leaves = PCPX_RANGE_PACKED_LEAVES > 0 && (!FILL || PCPX_RANGE_PACKED_FILL);
+    constexpr bool packed_leaves = PCPX_RANGE_PACKED_LEAVES > 0 && (!FILL || PCPX_RANGE_PACKED_FILL) && MOM == 0;
     static_assert(PCPX_RANGE_PACKED_LEAVES <= 32, "one row of LDS per wave");
     auto packed_leaf = [&](const Leaf* record, const u64 who, const u32 how_many) {
         u32 lane_here = lane;
@@ -182,7 +210,33 @@ __device__ __forceinline__ void range_group(const TreeView& t, const QueryView& 
             for (u32 leaf = loc * UNIT_LEAVES; leaf < (loc + 1u) * UNIT_LEAVES && leaf < t.nleaves; ++leaf) leaf_points(leaf);
         }
     }
-    if (valid && !FILL) out_cnt[(SELF && qv.by_position) ? p + qv.pos_bias : row] = cnt;
+    if constexpr (MOM != 0) {
+        if (!valid) return;
+        // epilogue: C = Q - S (S / n); n = 0 (an empty sphere) gives C = 0 -- the reference's empty scatter matrix -- and NaN for
+        // the centroid and the mean distance (0 / 0), as pcp::estimate_normal and average_distances_to_neighbors do
+        const float fn = static_cast<float>(cnt);
+        const float m0 = s0 / fn, m1 = s1 / fn, m2 = s2 / fn;
+        const u64 r3 = 3ull * row;
+        if (mo.normals) {
+            const bool any = cnt != 0u;
+            const float c00 = any ? q00 - s0 * m0 : 0.f, c10 = any ? q10 - s1 * m0 : 0.f, c11 = any ? q11 - s1 * m1 : 0.f;
+            const float c20 = any ? q20 - s2 * m0 : 0.f, c21 = any ? q21 - s2 * m1 : 0.f, c22 = any ? q22 - s2 * m2 : 0.f;
+            float nrm[3], ev[3];
+            eig3_smallest(c00, c10, c20, c11, c21, c22, nrm, ev);
+            mo.normals[r3] = nrm[0];
+            mo.normals[r3 + 1] = nrm[1];
+            mo.normals[r3 + 2] = nrm[2];
+        }
+        if (mo.centroids) {
+            mo.centroids[r3] = qx + m0;
+            mo.centroids[r3 + 1] = qy + m1;
+            mo.centroids[r3 + 2] = qz + m2;
+        }
+        if (MOM == 2 && mo.mean_dist) mo.mean_dist[row] = dsum / fn;
+        if (mo.count) mo.count[row] = cnt;
+    } else {
+        if (valid && !FILL) out_cnt[(SELF && qv.by_position) ? p + qv.pos_bias : row] = cnt;
+    }
 }
 
 // One single-wave workgroup per group, XCD-aware block order (pcpx_device.h: virtual_block).  (Tried: a persistent grid
@@ -199,6 +253,39 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void k_range(TreeView t, Quer
     if (g >= group_end) return;
     if (lane < 32u) published[wave_in_block()][lane].w = -1.f;  // packed_leaf's invariant: a slot that holds no centre holds r^2 = -1
     range_group<SELF, FILL>(t, qv, g, radius, radii, out_cnt, offsets, out_idx, published[wave_in_block()], lane);
+}
+
+// The moments form: one lane per sphere as k_range, no LDS (lane-per-range leaves); outputs by input row (self) or query row (batch)
+template <bool SELF, int MOM>
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void k_range_moments(TreeView t, QueryView qv, u32 group_first, u32 group_end, float radius,
+                                                                       const float* __restrict__ radii, MomentsOut mo)
+{
+    const u32 lane = threadIdx.x & 63u;
+    const u32 g = group_first + virtual_block() * WAVES_PER_BLOCK + wave_in_block();
+    if (g >= group_end) return;
+    range_group<SELF, false, MOM>(t, qv, g, radius, radii, nullptr, nullptr, nullptr, nullptr, lane, mo);
+}
+
+// the empty-set values at the rows of the points that are not indexed (position_of = 0xFFFFFFFF: outside the voxel grid)
+__global__ __launch_bounds__(256) void k_range_moments_empty_rows(const u32* __restrict__ pos_of, u64 n_rows, MomentsOut mo)
+{
+    const u64 i = blockIdx.x * static_cast<u64>(blockDim.x) + threadIdx.x;
+    if (i >= n_rows || pos_of[i] != 0xFFFFFFFFu) return;
+    const float nan = __builtin_nanf("");
+    if (mo.normals) {
+        float nrm[3], ev[3];
+        eig3_smallest(0.f, 0.f, 0.f, 0.f, 0.f, 0.f, nrm, ev);  // (what the epilogue gives for n = 0)
+        mo.normals[3 * i] = nrm[0];
+        mo.normals[3 * i + 1] = nrm[1];
+        mo.normals[3 * i + 2] = nrm[2];
+    }
+    if (mo.centroids) {
+        mo.centroids[3 * i] = nan;
+        mo.centroids[3 * i + 1] = nan;
+        mo.centroids[3 * i + 2] = nan;
+    }
+    if (mo.mean_dist) mo.mean_dist[i] = nan;
+    if (mo.count) mo.count[i] = 0u;
 }
 
 // AABB ranges: one wave per 64 boxes, no spatial coherence assumed (boxes are few in practice:
@@ -559,6 +646,44 @@ int launch_range_fill_self(Index& ix, u64 group_first, u64 group_count, float ra
                                                                                  static_cast<u32>(group_first + group_count), radius, nullptr, nullptr,
                                                                                  d_offsets, d_out_idx);
     return check_hip(hipGetLastError(), "k_range self fill launch", __FILE__, __LINE__);
+}
+
+// The moments form over query groups [group_first, group_first + group_count) of qv (self: the index's own points, qv.pos_lo /
+// pos_hi the asked positions).  Any output may be null; the mean distance's sum is only formed when it is asked for.
+int launch_range_moments(Index& ix, const QueryView& qv, bool self, u64 group_first, u64 group_count, float radius, const float* d_radii,
+                         float* d_normals, float* d_centroids, float* d_mean_dist, u32* d_count)
+{
+    if (group_count == 0) return PCPX_OK;
+    const u32 grid = grid_for_groups(group_count);
+    const u32 gf = static_cast<u32>(group_first), ge = static_cast<u32>(group_first + group_count);
+    MomentsOut mo;
+    mo.normals = d_normals;
+    mo.centroids = d_centroids;
+    mo.mean_dist = d_mean_dist;
+    mo.count = d_count;
+    const dim3 block(64 * WAVES_PER_BLOCK);
+    ProfileScope prof(ix, PCPX_K_RANGE);
+    if (self) {
+        if (d_mean_dist) k_range_moments<true, 2><<<grid, block, 0, ix.stream>>>(ix.view(), qv, gf, ge, radius, d_radii, mo);
+        else k_range_moments<true, 1><<<grid, block, 0, ix.stream>>>(ix.view(), qv, gf, ge, radius, d_radii, mo);
+    } else {
+        if (d_mean_dist) k_range_moments<false, 2><<<grid, block, 0, ix.stream>>>(ix.view(), qv, gf, ge, radius, d_radii, mo);
+        else k_range_moments<false, 1><<<grid, block, 0, ix.stream>>>(ix.view(), qv, gf, ge, radius, d_radii, mo);
+    }
+    return check_hip(hipGetLastError(), "k_range_moments launch", __FILE__, __LINE__);
+}
+
+int launch_range_moments_empty_rows(Index& ix, const u32* d_pos_of, u64 n_rows, float* d_normals, float* d_centroids, float* d_mean_dist,
+                                    u32* d_count)
+{
+    if (n_rows == 0) return PCPX_OK;
+    MomentsOut mo;
+    mo.normals = d_normals;
+    mo.centroids = d_centroids;
+    mo.mean_dist = d_mean_dist;
+    mo.count = d_count;
+    k_range_moments_empty_rows<<<static_cast<u32>((n_rows + 255) / 256), 256, 0, ix.stream>>>(d_pos_of, n_rows, mo);
+    return check_hip(hipGetLastError(), "k_range_moments_empty_rows launch", __FILE__, __LINE__);
 }
 
 int launch_aabb_count(Index& ix, const float* d_boxes6, u64 nb, u32* d_out_cnt)

@@ -213,6 +213,51 @@ class Index:
         check(self._lib.pcpx_range_aabb_batch(self._h, _vp(b), len(b), _vp(off), _vp(out), len(out)))
         return off, out
 
+    # ---- fixed-radius neighbourhoods (include/pcpx_radius.h) ----
+    @staticmethod
+    def _moments_outputs(rows, normals, centroids, mean_dist, counts):
+        if not (normals or centroids or mean_dist or counts):
+            raise ValueError("ask for at least one of normals, centroids, mean_dist, counts")
+        return (np.empty((rows, 3), np.float32) if normals else None, np.empty((rows, 3), np.float32) if centroids else None,
+                np.empty(rows, np.float32) if mean_dist else None, np.empty(rows, np.uint32) if counts else None)
+
+    @staticmethod
+    def _moments_result(outs):
+        got = tuple(o for o in outs if o is not None)
+        return got[0] if len(got) == 1 else got
+
+    def range_neighbourhoods_self(self, radius, normals=True, centroids=False, mean_dist=False, counts=False):
+        """Per indexed point, over every point within `radius` (itself included): the PCA normal (n x 3), the centroid (n x 3), the
+        mean distance (n) and the count (n), in input order -- what estimate_normals, estimate_tangent_planes and
+        average_distances_to_neighbors give with a range_search(sphere) map.  Returns the asked outputs in that order (one array
+        alone when one is asked).  An empty neighbourhood (a point outside the voxel grid): normal (0, 0, 1), NaN centroid and
+        mean distance, count 0."""
+        outs = self._moments_outputs(self.n_in, normals, centroids, mean_dist, counts)
+        check(self._lib.pcpx_range_neighbourhoods_self(self._h, float(radius), *(_vp(o) for o in outs)))
+        return self._moments_result(outs)
+
+    def range_neighbourhoods(self, queries, radius, normals=True, centroids=False, mean_dist=False, counts=False):
+        """The same for arbitrary spheres: centres `queries` (m x 3), `radius` a scalar or one radius per sphere."""
+        q = _f32(queries, 3)
+        radii = None
+        r = 0.0
+        if np.ndim(radius) == 0:
+            r = float(radius)
+        else:
+            radii = _f32(radius).reshape(-1)
+            if len(radii) != len(q):
+                raise ValueError("one radius per sphere")
+        outs = self._moments_outputs(len(q), normals, centroids, mean_dist, counts)
+        check(self._lib.pcpx_range_neighbourhoods_batch(self._h, _vp(q), _vp(radii), r, len(q), *(_vp(o) for o in outs)))
+        return self._moments_result(outs)
+
+    def range_neighbourhoods_self_dev(self, radius, d_normals=None, d_centroids=None, d_mean_dist=None, d_counts=None, first=0,
+                                      count=_capi.UINT64_MAX):
+        """Device form (pointers to device arrays by input row; any may be None, not all), enqueued on the index's stream: the rows of
+        the curve positions [first, first + count) -- plus, when that is the whole order, the rows of points outside the grid."""
+        check(self._lib.pcpx_range_neighbourhoods_self_dev(self._h, float(radius), first, count,
+                                                           *(C.c_void_p(d) if d else None for d in (d_normals, d_centroids, d_mean_dist, d_counts))))
+
     # ---- normals ----
     def normals_knn_self(self, k, eps=1e-5, want_knn=False):
         nrm = np.empty((self.n_in, 3), np.float32)
