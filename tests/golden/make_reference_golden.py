@@ -5,6 +5,7 @@ for the GPU tests in tests/test_gpu_reference_golden.py, which cannot build the 
 
 Deterministic (fixed seeds, sequential reference calls, no timestamps in the archives): a second run writes the same bytes.
 Clouds are stored as small integers with a power-of-two scale, so every coordinate is exact in float32 and compresses well."""
+import hashlib
 import io
 import os
 import sys
@@ -17,6 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import far_cloud_cases as FC  # noqa: E402
 import surface_nets_model as M  # noqa: E402
 from oracle import pcp_ref as R  # noqa: E402
 
@@ -181,10 +183,45 @@ def wlop():
     return _save("ref_wlop.npz", **out)
 
 
+def _sha(a):
+    return np.frombuffer(hashlib.sha256(np.ascontiguousarray(a).tobytes()).digest(), np.uint8)
+
+
+FAR_KNN = (("far_1e3", 1e-5), ("utm", 1e-5), ("utm", 0.0), ("small", 1e-5), ("small", 0.0))
+FAR_RANGE = ("cad_mm", "utm")
+def far():
+    """The clouds of tests/far_cloud_cases.py are rebuilt by the test (only their SHA-256 is stored): octree kNN rows at
+    far_1e3, utm and small (eps 1e-5 and 0); lists of spheres with one radius each at cad_mm (r > 1 throughout) and utm (r
+    <= 1 and > 1); both surface-nets overloads on a grid at 2^14."""
+    out = {}
+    for name, eps in FAR_KNN:
+        c = FC.case(name)
+        key = "knn_%s_eps%d" % (name, int(eps > 0))
+        rows = c.rows[:500].astype(np.uint32)
+        out[name + "_sha"] = _sha(c.points)
+        out[key + "_rows"] = rows
+        out[key + "_idx"], out[key + "_cnt"] = R.Octree(c.points).knn(c.points[rows], 15, eps)
+    for name in FAR_RANGE:
+        c = FC.case(name)
+        rng = np.random.default_rng(505)
+        out[name + "_sha"] = _sha(c.points)
+        centres = c.points[c.rows[:128]].copy()
+        centres[64:] = (centres[64:] + rng.uniform(-1, 1, (64, 3)) * F(c.radius)).astype(F)
+        radii = np.tile(np.array([c.radius, 2 * c.radius, 1.5, 0.75 * c.radius], F), 32)
+        t = R.Octree(c.points)
+        out["range_%s_centres" % name], out["range_%s_radii" % name] = centres.astype(F), radii
+        out["range_%s_off" % name], out["range_%s_idx" % name] = _csr([t.range_sphere(x, r) for x, r in zip(centres, radii)])
+    g, f, iso, hint = FC.far_grid()
+    out["grid_v"], out["grid_t"] = R.surface_nets(f, g, iso)
+    out["grid_hint_v"], out["grid_hint_t"] = R.surface_nets(f, g, iso, hint=hint, outside=1.0)
+    out["grid_field_sha"] = _sha(f)
+    return _save("ref_far.npz", **out)
+
+
 def main():
     if not R.available():
         sys.exit("no build of the reference: %s" % R.why_unavailable())
-    total = knn() + ranges() + kd() + surface() + wlop()
+    total = knn() + ranges() + kd() + surface() + wlop() + far()
     print("%-24s %7d bytes" % ("total", total))
     assert total <= 1536 * 1024
 
