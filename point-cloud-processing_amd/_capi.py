@@ -207,6 +207,15 @@ RADIUS_SIGNATURES = {
 }
 
 
+# name -> (restype, argtypes); every symbol declared in include/pcpx_cluster.h (radius-connected components and DBSCAN)
+PCPX_CLUSTER_NOISE = 0xFFFFFFFF
+PCPX_CLUSTER_COMPACT = 1
+CLUSTER_SIGNATURES = {
+    "pcpx_cluster_self_dev": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcpx_cluster_self": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, u64p]),
+}
+
+
 def load():
     """Load libpcpx.so; raises if it has not been built (run __graft_entry__.build())."""
     global _lib
@@ -218,7 +227,7 @@ def load():
             "There is no CPU fallback for the pcpx compute path." % LIB_PATH)
     _share_hip_runtime_with_torch()
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(RADIUS_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(RADIUS_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

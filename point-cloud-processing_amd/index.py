@@ -258,6 +258,34 @@ class Index:
         check(self._lib.pcpx_range_neighbourhoods_self_dev(self._h, float(radius), first, count,
                                                            *(C.c_void_p(d) if d else None for d in (d_normals, d_centroids, d_mean_dist, d_counts))))
 
+    # ---- clustering (include/pcpx_cluster.h) ----
+    def cluster(self, radius, min_pts=1, compact=True, want_core=False, want_counts=False):
+        """Radius-connected components (min_pts = 1) or DBSCAN of the indexed cloud: two points are joined iff one is in the other's
+        sphere (the rule of range_count_self), a point is core iff its sphere holds >= min_pts points (itself included), clusters are
+        the connected components of the core points, a non-core point with a core neighbour joins the smallest-labelled one's
+        cluster, every other point (and every point outside the voxel grid) is noise: label 0xFFFFFFFF.  compact: labels
+        0 ... C-1 ordered by representative, else the representative itself (the cluster's smallest core input index).
+        Returns (labels uint32 (n_in,), number of clusters[, core bool (n_in,)][, counts uint32 (n_in,)])."""
+        labels = np.empty(self.n_in, np.uint32)
+        core = np.empty(self.n_in, np.uint8) if want_core else None
+        counts = np.empty(self.n_in, np.uint32) if want_counts else None
+        nclusters = C.c_uint64(0)
+        check(self._lib.pcpx_cluster_self(self._h, float(radius), int(min_pts), _capi.PCPX_CLUSTER_COMPACT if compact else 0, _vp(labels),
+                                          _vp(core), _vp(counts), C.byref(nclusters)))
+        out = (labels, int(nclusters.value))
+        if want_core:
+            out += (core.astype(bool),)
+        if want_counts:
+            out += (counts,)
+        return out
+
+    def cluster_dev(self, radius, d_labels, min_pts=1, compact=True, d_core=None, d_counts=None, d_cluster_count=None):
+        """Device form (pointers to device arrays by input row: labels uint32, core uint8, counts uint32; d_cluster_count one
+        uint64), enqueued on the index's stream."""
+        check(self._lib.pcpx_cluster_self_dev(self._h, float(radius), int(min_pts), _capi.PCPX_CLUSTER_COMPACT if compact else 0,
+                                              C.c_void_p(d_labels) if d_labels else None,
+                                              *(C.c_void_p(d) if d else None for d in (d_core, d_counts, d_cluster_count))))
+
     # ---- normals ----
     def normals_knn_self(self, k, eps=1e-5, want_knn=False):
         nrm = np.empty((self.n_in, 3), np.float32)
