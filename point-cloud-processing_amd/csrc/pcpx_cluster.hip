@@ -1,8 +1,10 @@
 // pcpx_cluster.hip -- radius-connected components and DBSCAN of the indexed cloud (include/pcpx_cluster.h):
-// a fourth form of the sphere walk of pcpx_range.hip (one lane per self sphere, lane-per-range leaves) that feeds every in-range
-// pair to a union-find over CURVE POSITIONS and writes no neighbour list, a second walk that gives the border points their label,
-// and the passes that turn roots into labels by input row.
+// the leaf-direct sphere walk of pcpx_device.h (one lane per self sphere, lane-per-range leaves) feeds every in-range pair to the
+// union-find of pcpx_unionfind.h over CURVE POSITIONS and writes no neighbour list, a second walk gives the border points their
+// label, and the passes after it turn roots into labels by input row.
 #include "pcpx_device.h"
+#include "pcpx_scan.h"
+#include "pcpx_unionfind.h"
 #include "pcpx_cluster.h"
 
 namespace pcpx {
@@ -13,98 +15,12 @@ constexpr u32 NOT_CORE = 0xFFFFFFFFu;  // parent word of a position that holds n
 static_assert(NOT_CORE == PCPX_CLUSTER_NOISE, "a non-core position's parent word is the noise label");
 constexpr u32 CL_BLOCK = 256;
 
-// ---- the union-find: the ECL-CC scheme of pcpx_isosurface.hip, restated over curve positions ------------
-// parent[v] <= v always, a root is its own parent, a hook links the larger of two roots under the smaller with a CAS: every root is
-// the smallest position of its tree, and the final root of a component is its smallest core position whatever order the hooks ran
-// in.  Only core positions are vertices; the word of any other position holds NOT_CORE and is never followed.
-//
-// Coherence: the parent words are written by other workgroups, on other XCDs, within the hook launch, so every access to them
-// there is an agent-scope atomic (relaxed: no other data is handed over through them).  Any value parent[x] ever held is an
-// ancestor of x and stays one: a stale or overwritten halving store only lengthens a later walk, and two positions that show the
-// same ancestor are in one tree.  A CAS succeeds only on a word that still holds its own index (a root).
-// Progress: no lane waits for another.  A climb ends because parents strictly decrease; a failed CAS means another lane hooked
-// that root meanwhile -- there are fewer than n hooks in all -- and the retry climbs from what the CAS returned.
-__device__ __forceinline__ u32 uf_load(const u32* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ u32 uf_root(u32* parent, u32 x)
-{
-    u32 cur = uf_load(parent + x);
-    if (cur != x) {
-        u32 prev = x, next;
-        while (cur > (next = uf_load(parent + cur))) {
-            __hip_atomic_store(parent + prev, next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // path halving
-            prev = cur;
-            cur = next;
-        }
-    }
-    return cur;
-}
-
-// joins the trees of two core positions; `a` = a known ancestor of the first (the lane's own root so far), returns the joined root
-__device__ __forceinline__ u32 uf_unite(u32* parent, u32 a, u32 q)
-{
-    a = uf_root(parent, a);
-    u32 r = uf_root(parent, q);
-    while (a != r) {
-        u32 lo = a < r ? a : r, hi = a < r ? r : a;
-        if (__hip_atomic_compare_exchange_strong(parent + hi, &hi, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-            return lo;
-        a = uf_root(parent, hi);  // hi now holds the parent it was given meanwhile
-        r = uf_root(parent, lo);
-    }
-    return a;
-}
-
-// ---- the sphere walk of range_group (pcpx_range.hip), lane-per-range leaves, with the leaf's number handed to the caller --------
-// leaf_fn(leaf, record) is called, in curve order, for every leaf below `leaf_end` whose box some lane's sphere reaches.  The walk is
-// depth first in curve order, so the first node that starts at or beyond leaf_end ends it: the hook form only looks at partners
-// EARLIER in curve order than its own group, about half of a full walk.
-template <class LeafFn>
-__device__ __forceinline__ void sphere_walk(const TreeView& t, const float qx, const float qy, const float qz, const float r2,
-                                            const u32 leaf_end, LeafFn&& leaf_fn)
-{
-    auto need = [&](const NodeBox& b) { return box_d2(b, qx, qy, qz) <= r2; };
-    WalkerT<true, false> wk;
-    u32 nexp = 0;
-    if (wk.start(t, need, nexp))  // the root is the only unit
-        for (u32 leaf = 0; leaf < static_cast<u32>(UNIT_LEAVES) && leaf < t.nleaves && leaf < leaf_end; ++leaf)
-            leaf_fn(leaf, load_const(t.leaves + leaf));
-    while (!wk.done()) {  // one pop per trip; a last-level node looks at its needed leaves itself (no tree has depth 1: no leaf is popped)
-        u32 loc;
-        const int h = wk.pop(loc);
-        if ((static_cast<u64>(loc) << (LOGW * h)) * UNIT_LEAVES >= leaf_end) break;  // this node and all that are pending lie later
-        if (h > 1) {
-            wk.expand(t, h, loc, need);
-        } else {
-            const u32 needed = wk.leaves_of(t, loc, need);
-            const Leaf* records = t.leaves + (loc << LOGW) * UNIT_LEAVES;
-#pragma unroll
-            for (int c = 0; c < W; ++c) {
-                if ((needed >> c) & 1u) {
-#pragma unroll
-                    for (int r = 0; r < UNIT_LEAVES; ++r) {
-                        const u32 leaf = ((loc << LOGW) + c) * UNIT_LEAVES + r;
-                        if (leaf >= t.nleaves || leaf >= leaf_end) break;
-                        leaf_fn(leaf, load_const(records + c * UNIT_LEAVES + r));
-                    }
-                }
-            }
-        }
-    }
-}
+// The union-find (pcpx_unionfind.h) runs over curve positions: only core positions are vertices; the word of any other position
+// holds NOT_CORE and is never followed.  The final root of a component is its smallest core position.
 
 struct Labels8 {
     u32 v[LEAF];
 };
-
-// the point of curve position p (p < t.n)
-__device__ __forceinline__ void point_at(const TreeView& t, u32 p, float& x, float& y, float& z)
-{
-    const Leaf& lf = t.leaves[p / LEAF];
-    x = lf.x[p % LEAF];
-    y = lf.y[p % LEAF];
-    z = lf.z[p % LEAF];
-}
 
 // One thread per leaf slot (npos = 8 nleaves of them): the core flag into the parent word, the outputs that are known by now by
 // input row, and aux[p] = NOT_CORE for the representatives' atomicMin.  count_at: the sphere counts BY POSITION (null: min_pts = 1,
@@ -135,15 +51,19 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void k_cluster_hook(TreeView 
     const u32 g = virtual_block() * WAVES_PER_BLOCK + wave_in_block();
     if (g >= group_end) return;
     const u32 p = g * GROUP + lane;
-    float qx = 0.f, qy = 0.f, qz = 0.f;
+    LaneQuery c{0.f, 0.f, 0.f, 0u};
     u32 mine = NOT_CORE;
     if (p < t.n) {
-        point_at(t, p, qx, qy, qz);
+        c = lane_query<true>(t, QueryView{}, p);
         mine = uf_load(parent + p);
     }
+    const float qx = c.x, qy = c.y, qz = c.z;
     const float r2 = mine != NOT_CORE ? radius * radius : -1.f;  // sphere.hpp:34 radius * radius in float; -1: idle lane
     if (!any_lane(mine != NOT_CORE)) return;
-    sphere_walk(t, qx, qy, qz, r2, (g + 1u) * (GROUP / LEAF), [&](const u32 leaf, const Leaf& lf) {
+    auto need = [&](const NodeBox& b) { return box_d2(b, qx, qy, qz) <= r2; };
+    // only partners EARLIER in curve order than the group's own end: about half of a full walk
+    walk_needed_leaves<false, true>(t, need, [&](const u32 leaf, const Leaf* record, u64, u32) {
+        const Leaf lf = load_const(record);
 #pragma unroll
         for (int j = 0; j < LEAF; ++j) {
             const float dx = lf.x[j] - qx, dy = lf.y[j] - qy, dz = lf.z[j] - qz;
@@ -153,14 +73,10 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void k_cluster_hook(TreeView 
                 if (seen != NOT_CORE && seen != mine) mine = uf_unite(parent, mine, q);
             }
         }
-    });
+    }, (g + 1u) * (GROUP / LEAF));
 }
 
-// parent[p] = the root of p, in a launch after the hooks: the roots are fixed.  The climb here only READS (no path halving): a
-// halving store is a read of parent[x] followed later by a store of an ancestor over it, and one that straddled thread x's own
-// store of its root would put a lower ancestor back.  With reads only, the one store to parent[p] in this launch is its root, and
-// a climb that passes through p sees either the old ancestor or the root: both lead to the same root.  (The hooks' halving has
-// left the paths short.)
+// parent[p] = the root of p, in a launch after the hooks, by the read-only climb (uf_find, pcpx_unionfind.h).
 // The representative of a root = the smallest input index among its core points: an atomicMin per point on the root's word of aux
 // would serialise a 10 M-point component on one address (measured: 113 ms of a 119 ms call), so a wave first folds the lanes that
 // share the first active lane's root into one atomic, twice, and a lane that is left only issues its atomic if the word it reads
@@ -171,7 +87,7 @@ __global__ __launch_bounds__(CL_BLOCK) void k_cluster_flatten(TreeView t, u32* p
     u32 r = p < t.n ? uf_load(parent + p) : NOT_CORE;
     u32 id = NOT_CORE;
     if (r != NOT_CORE) {
-        for (u32 up; r > (up = uf_load(parent + r));) r = up;
+        r = uf_find(parent, r);
         __hip_atomic_store(parent + p, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         id = t.leaves[p / LEAF].id[p % LEAF];
     }
@@ -211,16 +127,19 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void k_cluster_border(TreeVie
     if (g >= group_end) return;
     const u32 p = g * GROUP + lane;
     const bool valid = p < t.n;
-    float qx = 0.f, qy = 0.f, qz = 0.f;
+    LaneQuery c{0.f, 0.f, 0.f, 0u};
     u32 best = NOT_CORE;
     if (valid) {
-        point_at(t, p, qx, qy, qz);
+        c = lane_query<true>(t, QueryView{}, p);
         best = label_at[p];
     }
+    const float qx = c.x, qy = c.y, qz = c.z;
     const bool border = valid && best == NOT_CORE;
     const float r2 = border ? radius * radius : -1.f;
     if (any_lane(border)) {
-        sphere_walk(t, qx, qy, qz, r2, t.nleaves, [&](const u32 leaf, const Leaf& lf) {
+        auto need = [&](const NodeBox& b) { return box_d2(b, qx, qy, qz) <= r2; };
+        walk_needed_leaves<false>(t, need, [&](const u32 leaf, const Leaf* record, u64, u32) {
+            const Leaf lf = load_const(record);
             const Labels8 lb = load_const(reinterpret_cast<const Labels8*>(label_at + static_cast<u64>(leaf) * LEAF));
 #pragma unroll
             for (int j = 0; j < LEAF; ++j) {
@@ -241,83 +160,10 @@ __global__ __launch_bounds__(CL_BLOCK) void k_cluster_rows(TreeView t, const u32
 }
 
 // ---- the number of clusters and the compact ids: row i is a representative iff labels[i] == i; exclusive scan of that flag ------
-constexpr u32 CL_TILE = 1024;
-__global__ __launch_bounds__(256) void k_cluster_tile_sums(const u32* __restrict__ labels, u32 n, u32* __restrict__ tile_sum)
-{
-    __shared__ u32 w[4];
-    const u32 base = blockIdx.x * CL_TILE;
-    u32 v = 0;
-#pragma unroll
-    for (u32 j = 0; j < CL_TILE / 256; ++j) {
-        const u32 i = base + j * 256 + threadIdx.x;
-        v += (i < n && labels[i] == i) ? 1u : 0u;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    if ((threadIdx.x & 63u) == 0) w[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = w[0] + w[1] + w[2] + w[3];
-}
-// one block: tile sums -> their exclusive scan in place, and the total
-__global__ __launch_bounds__(1024) void k_cluster_scan_sums(u32* __restrict__ tile_sum, u32 ntiles, u64* __restrict__ total_out)
-{
-    __shared__ u32 wsum[16];
-    __shared__ u32 carry_s;
-    const u32 t = threadIdx.x, lane = t & 63u, w = t >> 6;
-    if (t == 0) carry_s = 0;
-    __syncthreads();
-    for (u32 base = 0; base < ntiles; base += 1024) {
-        const u32 i = base + t;
-        const u32 v = i < ntiles ? tile_sum[i] : 0u;
-        u32 incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const u32 up = __shfl_up(incl, off);
-            if (lane >= static_cast<u32>(off)) incl += up;
-        }
-        if (lane == 63) wsum[w] = incl;
-        __syncthreads();
-        u32 before = carry_s, total = 0;
-        for (u32 j = 0; j < 16; ++j) {
-            before += j < w ? wsum[j] : 0u;
-            total += wsum[j];
-        }
-        if (i < ntiles) tile_sum[i] = before + incl - v;
-        __syncthreads();
-        if (t == 0) carry_s += total;
-        __syncthreads();
-    }
-    if (t == 0 && total_out) *total_out = carry_s;
-}
-// rank[i] = representatives among rows [0, i)
-__global__ __launch_bounds__(256) void k_cluster_ranks(const u32* __restrict__ labels, u32 n, const u32* __restrict__ tile_base, u32* __restrict__ rank)
-{
-    __shared__ u32 w[4];
-    const u32 base = blockIdx.x * CL_TILE + threadIdx.x * (CL_TILE / 256);
-    u32 c[CL_TILE / 256], s = 0;
-#pragma unroll
-    for (u32 j = 0; j < CL_TILE / 256; ++j) {
-        c[j] = (base + j < n && labels[base + j] == base + j) ? 1u : 0u;
-        s += c[j];
-    }
-    const u32 lane = threadIdx.x & 63u;
-    u32 incl = s;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const u32 up = __shfl_up(incl, off);
-        if (lane >= static_cast<u32>(off)) incl += up;
-    }
-    if (lane == 63) w[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    u32 before = 0;
-    for (u32 j = 0; j < (threadIdx.x >> 6); ++j) before += w[j];
-    u32 at = tile_base[blockIdx.x] + before + incl - s;
-#pragma unroll
-    for (u32 j = 0; j < CL_TILE / 256; ++j) {
-        if (base + j < n) rank[base + j] = at;
-        at += c[j];
-    }
-}
+struct IsRepresentative {
+    const u32* labels;
+    __device__ u32 operator()(u32 i) const { return labels[i] == i ? 1u : 0u; }
+};
 // labels[i] = rank of its representative (in place: a thread reads and writes its own row of labels)
 __global__ __launch_bounds__(CL_BLOCK) void k_cluster_compact(u32* __restrict__ labels, u32 n, const u32* __restrict__ rank)
 {
@@ -365,7 +211,7 @@ int cluster_self(Index& ix, float radius, u32 min_pts, u32 flags, u32* d_labels,
         return PCPX_OK;
     }
     const u64 npos = static_cast<u64>(ix.nleaves) * LEAF;  // >= n
-    const u32 ntiles = blocks_of(rows, CL_TILE);
+    const u32 ntiles = scan_tiles(rows);
     auto padded = [](u64 words) { return (words * sizeof(u32) + 255) / 256 * 256; };
     const size_t parent_bytes = padded(npos > rows ? npos : rows), aux_bytes = padded(npos ? npos : 1), sums_bytes = padded(ntiles + 1);
     if ((st = ensure_scratch(ix, parent_bytes + aux_bytes + sums_bytes)) != PCPX_OK) return st;
@@ -405,14 +251,9 @@ int cluster_self(Index& ix, float radius, u32 min_pts, u32 flags, u32* d_labels,
     }
     const bool compact = (flags & PCPX_CLUSTER_COMPACT) != 0;
     if (compact || d_cluster_count) {
-        const u32 n32 = static_cast<u32>(rows);
-        k_cluster_tile_sums<<<ntiles, 256, 0, s>>>(d_labels, n32, sums);
-        k_cluster_scan_sums<<<1, 1024, 0, s>>>(sums, ntiles, d_cluster_count);
-        if (compact) {
-            u32* rank = parent;  // (free by now)
-            k_cluster_ranks<<<ntiles, 256, 0, s>>>(d_labels, n32, sums, rank);
-            k_cluster_compact<<<blocks_of(rows, CL_BLOCK), CL_BLOCK, 0, s>>>(d_labels, n32, rank);
-        }
+        u32* rank = compact ? parent : nullptr;  // (free by now); rank[i] = representatives among rows [0, i)
+        if ((st = exclusive_scan(IsRepresentative{d_labels}, rows, sums, rank, d_cluster_count, s)) != PCPX_OK) return st;
+        if (compact) k_cluster_compact<<<blocks_of(rows, CL_BLOCK), CL_BLOCK, 0, s>>>(d_labels, static_cast<u32>(rows), rank);
         PCPX_HIP(hipGetLastError());
     }
     return PCPX_OK;

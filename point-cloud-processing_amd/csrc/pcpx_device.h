@@ -220,6 +220,66 @@ struct WalkerT {
 };
 using Walker = WalkerT<true, false>;
 
+// The leaf-direct walk: leaf_fn(leaf, record, who, how_many) is called, in curve order, for every leaf record whose box some
+// lane needs -- leaf = its number, record = its address (the callee loads what it reads of it), and with KEEP who = the ballot
+// of the lanes that need it and how_many = their number (without: all lanes, GROUP).  "Is there another leaf" is in the
+// control flow rather than in a value (WalkerT::pop).  A last-level node looks at its needed leaves itself (leaves_of)
+// instead of pushing and popping them: the four children written out, so that a child's record is an immediate offset from
+// the node's first leaf and its lanes' ballot a register pair known at compile time.  No tree has depth 1 (depth_of,
+// pcpx_build.hip), so no leaf is ever popped; the children of a last-level node are UNITS of UNIT_LEAVES records under one box.
+// BOUNDED: only the leaves below leaf_end.  The walk is depth first in curve order, so the first node that starts at or
+// beyond leaf_end ends it.
+// (k_range_aabb, pcpx_range.hip, keeps a second form with the children in a scalar loop: 133 scalar registers fewer there.)
+template <bool KEEP, bool BOUNDED = false, class Need, class LeafFn>
+__device__ __forceinline__ void walk_needed_leaves(const TreeView& t, Need&& need, LeafFn&& leaf_fn, const u32 leaf_end = 0u)
+{
+    WalkerT<true, KEEP> wk;
+    u32 nexp = 0;
+    if (wk.start(t, need, nexp))  // the root is the only unit
+        for (u32 leaf = 0; leaf < static_cast<u32>(UNIT_LEAVES) && leaf < t.nleaves && (!BOUNDED || leaf < leaf_end); ++leaf)
+            leaf_fn(leaf, t.leaves + leaf, ~0ull, static_cast<u32>(GROUP));
+    while (!wk.done()) {  // one pop per trip
+        u32 loc;
+        const int h = wk.pop(loc);
+        if (BOUNDED && (static_cast<u64>(loc) << (LOGW * h)) * UNIT_LEAVES >= leaf_end) break;  // this node and all that are pending lie later
+        if (h > 1) {
+            wk.expand(t, h, loc, need);
+        } else {
+            const u32 needed = wk.leaves_of(t, loc, need);
+            const Leaf* records = t.leaves + (loc << LOGW) * UNIT_LEAVES;
+#pragma unroll
+            for (int c = 0; c < W; ++c) {
+                if ((needed >> c) & 1u) {
+                    u32 how_many = GROUP;
+                    if (KEEP) asm("s_bcnt1_i32_b64 %0, %1" : "=s"(how_many) : "s"(wk.leaf_need[c]) : "scc");
+#pragma unroll
+                    for (int r = 0; r < UNIT_LEAVES; ++r) {
+                        const u32 leaf = ((loc << LOGW) + c) * UNIT_LEAVES + r;
+                        if (UNIT_LEAVES > 1 && leaf >= t.nleaves) break;  // (the cloud's last unit may hold one leaf)
+                        if (BOUNDED && leaf >= leaf_end) break;
+                        leaf_fn(leaf, records + c * UNIT_LEAVES + r, KEEP ? wk.leaf_need[c] : ~0ull, how_many);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// The query of lane p (p below the number of queries): self = the point in leaf slot p, batch = sorted query p of qv.
+struct LaneQuery {
+    float x, y, z;
+    u32 row;  // its output row (self: the point's input index)
+};
+template <bool SELF>
+__device__ __forceinline__ LaneQuery lane_query(const TreeView& t, const QueryView& qv, const u32 p)
+{
+    if (SELF) {
+        const Leaf& lf = t.leaves[p / LEAF];
+        return LaneQuery{lf.x[p % LEAF], lf.y[p % LEAF], lf.z[p % LEAF], lf.id[p % LEAF]};
+    }
+    return LaneQuery{qv.qx[p], qv.qy[p], qv.qz[p], qv.row[p]};
+}
+
 inline u32 grid_for_groups(u64 groups)
 {
     u64 blocks = (groups + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;

@@ -132,22 +132,10 @@ __device__ __forceinline__ void visit_group(const TreeView& t, const QueryView& 
     const u32 p = g * GROUP + lane;
     const u32 nq = SELF ? t.n : qv.nq;
     const bool valid = p < nq;
-    float qx = 0.f, qy = 0.f, qz = 0.f;
-    u32 row = 0;
-    if (valid) {
-        if (SELF) {
-            const Leaf& lf = t.leaves[p / LEAF];
-            qx = lf.x[p % LEAF];
-            qy = lf.y[p % LEAF];
-            qz = lf.z[p % LEAF];
-            row = lf.id[p % LEAF];
-        } else {
-            qx = qv.qx[p];
-            qy = qv.qy[p];
-            qz = qv.qz[p];
-            row = qv.row[p];
-        }
-    }
+    LaneQuery q{0.f, 0.f, 0.f, 0u};
+    if (valid) q = lane_query<SELF>(t, qv, p);
+    const float qx = q.x, qy = q.y, qz = q.z;
+    const u32 row = q.row;
     const float r2 = valid ? radius * radius : -1.f;  // sphere.hpp:55 radius * radius in float; -1: idle lane
     acc.begin(qx, qy, qz, p, valid);
     auto need = [&](const NodeBox& b) { return box_d2(b, qx, qy, qz) <= r2; };

@@ -17,6 +17,8 @@
 // Hint-seeded surface nets (:653-1119 of the reference): the same passes restricted to one connected
 // component of the active cubes, found by a table-driven seed search and union-find labelling.
 #include "pcpx_internal.h"
+#include "pcpx_scan.h"
+#include "pcpx_unionfind.h"
 
 #include <algorithm>
 #include <array>
@@ -31,7 +33,6 @@ namespace {
 
 constexpr int SN_BLOCK = 256;
 constexpr u32 SN_MAX_BLOCKS = 8192;  // grid-stride beyond this: 256 CUs x 32 blocks of 256 threads cover the card many times over
-constexpr int SCAN_THREADS = 256, SCAN_ITEMS = 8, SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;
 constexpr u32 NO_VERTEX = 0xFFFFFFFFu;
 
 u32 blocks_for(u64 n)
@@ -111,98 +112,6 @@ __global__ __launch_bounds__(SN_BLOCK) void k_sdf_eval(GridDev g, Bricks b, u64 
         }
         field[corner_at(g, i, j, k)] = v;
     }
-}
-
-// ---- exclusive scan, in place, over n entries (the caller's last entry is 0 and receives the total) ------------------------
-
-template <class T>
-__device__ T block_exclusive_scan(T v, T* lds, T& total)
-{
-    const int t = threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-    for (int off = 1; off < SCAN_THREADS; off <<= 1) {
-        const T add = t >= off ? lds[t - off] : T(0);
-        __syncthreads();
-        lds[t] += add;
-        __syncthreads();
-    }
-    const T incl = lds[t];
-    total = lds[SCAN_THREADS - 1];
-    __syncthreads();
-    return incl - v;
-}
-
-template <class T>
-__global__ __launch_bounds__(SCAN_THREADS) void k_scan_reduce(const T* __restrict__ a, u64 n, T* __restrict__ sums)
-{
-    __shared__ T lds[SCAN_THREADS];
-    const u64 base = static_cast<u64>(blockIdx.x) * SCAN_TILE;
-    T s = 0;
-    for (int r = 0; r < SCAN_ITEMS; ++r) {
-        const u64 e = base + static_cast<u64>(r) * SCAN_THREADS + threadIdx.x;
-        if (e < n) s += a[e];
-    }
-    T total;
-    (void)block_exclusive_scan<T>(s, lds, total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-template <class T>
-__global__ __launch_bounds__(SCAN_THREADS) void k_scan_sums(T* __restrict__ sums, u64 ntiles)
-{
-    __shared__ T lds[SCAN_THREADS];
-    T carry = 0;
-    for (u64 base = 0; base < ntiles; base += SCAN_THREADS) {
-        const u64 e = base + threadIdx.x;
-        const T v = e < ntiles ? sums[e] : T(0);
-        T total;
-        const T ex = block_exclusive_scan<T>(v, lds, total);
-        if (e < ntiles) sums[e] = carry + ex;
-        carry += total;
-    }
-}
-
-template <class T>
-__global__ __launch_bounds__(SCAN_THREADS) void k_scan_apply(T* __restrict__ a, u64 n, const T* __restrict__ sums)
-{
-    __shared__ T tile[SCAN_TILE];
-    __shared__ T lds[SCAN_THREADS];
-    const u64 base = static_cast<u64>(blockIdx.x) * SCAN_TILE;
-    for (int r = 0; r < SCAN_ITEMS; ++r) {  // coalesced load into LDS
-        const int l = r * SCAN_THREADS + threadIdx.x;
-        tile[l] = base + l < n ? a[base + l] : T(0);
-    }
-    __syncthreads();
-    T mine[SCAN_ITEMS], s = 0;
-    for (int r = 0; r < SCAN_ITEMS; ++r) {  // thread t owns items [t*ITEMS, t*ITEMS + ITEMS) of the tile
-        mine[r] = s;
-        s += tile[threadIdx.x * SCAN_ITEMS + r];
-    }
-    T total;
-    const T ex = block_exclusive_scan<T>(s, lds, total) + sums[blockIdx.x];
-    for (int r = 0; r < SCAN_ITEMS; ++r) tile[threadIdx.x * SCAN_ITEMS + r] = ex + mine[r];
-    __syncthreads();
-    for (int r = 0; r < SCAN_ITEMS; ++r) {
-        const int l = r * SCAN_THREADS + threadIdx.x;
-        if (base + l < n) a[base + l] = tile[l];
-    }
-}
-
-template <class T>
-int exclusive_scan_in_place(T* d_a, u64 n, T* d_sums, hipStream_t s)
-{
-    const u64 tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
-    if (tiles == 0) return PCPX_OK;
-    if (tiles > 0x7FFFFFFFull) {
-        set_error("pcpx: scan of %llu entries is too long", static_cast<unsigned long long>(n));
-        return PCPX_ERR_INVALID;
-    }
-    k_scan_reduce<T><<<static_cast<u32>(tiles), SCAN_THREADS, 0, s>>>(d_a, n, d_sums);
-    k_scan_sums<T><<<1, SCAN_THREADS, 0, s>>>(d_sums, tiles);
-    k_scan_apply<T><<<static_cast<u32>(tiles), SCAN_THREADS, 0, s>>>(d_a, n, d_sums);
-    PCPX_HIP(hipGetLastError());
-    return PCPX_OK;
 }
 
 // ---- surface nets -------------------------------------------------------------------------------------------------------
@@ -437,35 +346,8 @@ __global__ __launch_bounds__(SN_BLOCK) void k_hint_nearest(GridDev g, u32 nvert,
     if (threadIdx.x == 0 && best[0] != ~0ull) atomicMin(seed + 1, best[0]);
 }
 
-// Connected components of the active cubes (two are adjacent iff they share a bipolar edge) by union-find over active ranks,
-// in the style of ECL-CC: parent[v] <= v always, a root is its own parent, a hook links the larger of two roots under the
-// smaller with a CAS.  So every root is the smallest rank of its tree and the final label of a component is its smallest
-// active rank, whatever the order the hooks ran in.
-//
-// Coherence: the parent words are written by other workgroups, on other XCDs, within the hook launch, so every access to
-// them there is an agent-scope atomic (relaxed: no other data is handed over through them).  Path halving stores an
-// ancestor over a non-root's parent; any value ever held by parent[x] is an ancestor of x and stays one, so a stale or
-// overwritten halving store only lengthens a later walk.  A CAS succeeds only on a word that still holds its own index (a
-// root); when it fails, both sides climb again from what it returned.
-__device__ __forceinline__ u32 cc_load(const u32* p)
-{
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ u32 cc_root(u32* parent, u32 x)
-{
-    u32 cur = cc_load(parent + x);
-    if (cur != x) {
-        u32 prev = x, next;
-        while (cur > (next = cc_load(parent + cur))) {
-            __hip_atomic_store(parent + prev, next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            prev = cur;
-            cur = next;
-        }
-    }
-    return cur;
-}
-
+// Connected components of the active cubes (two are adjacent iff they share a bipolar edge) by the union-find of
+// pcpx_unionfind.h over active ranks: the final label of a component is its smallest active rank.
 __global__ __launch_bounds__(SN_BLOCK) void k_cc_init(u32 nvert, u32* __restrict__ parent)
 {
     for (u64 v = static_cast<u64>(blockIdx.x) * SN_BLOCK + threadIdx.x; v < nvert; v += static_cast<u64>(gridDim.x) * SN_BLOCK)
@@ -499,24 +381,18 @@ __global__ __launch_bounds__(SN_BLOCK) void k_cc_hook(GridDev g, u32 nvert, cons
                 continue;  // (outside the grid; dk >= 0 here)
             const u32 u = map[(i + di) + (j + dj) * g.sx + (k + dk) * (g.sx * g.sy)];  // (a cube on a bipolar edge is active)
             if (u == NO_VERTEX) continue;
-            u32 a = cc_root(parent, v), r = cc_root(parent, u);
-            while (a != r) {
-                u32 lo = a < r ? a : r, hi = a < r ? r : a;
-                if (__hip_atomic_compare_exchange_strong(parent + hi, &hi, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-                    break;
-                a = cc_root(parent, hi);  // hi now holds the parent it was given meanwhile
-                r = cc_root(parent, lo);
-            }
+            (void)uf_unite(parent, v, u);
         }
     }
 }
 
-// parent[v] = the root of v (a launch after the hooks: the roots are fixed, and the words this launch rewrites only ever
-// change from one ancestor to a higher one, so the walks read them with the same atomics and end at the same root)
+// parent[v] = the root of v, in a launch after the hooks: the roots are fixed.  The climb only READS (uf_find): a halving store
+// that straddled thread x's own store of its root would put a non-root back into parent[x], and k_cc_restrict compares the
+// words as roots.  With reads only, the one store to parent[v] in this launch is its root (pcpx_unionfind.h).
 __global__ __launch_bounds__(SN_BLOCK) void k_cc_flatten(u32 nvert, u32* parent)
 {
     for (u64 v = static_cast<u64>(blockIdx.x) * SN_BLOCK + threadIdx.x; v < nvert; v += static_cast<u64>(gridDim.x) * SN_BLOCK) {
-        const u32 r = cc_root(parent, static_cast<u32>(v));
+        const u32 r = uf_find(parent, static_cast<u32>(v));
         __hip_atomic_store(parent + v, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
@@ -599,7 +475,7 @@ int mesh_selected(const GridDev& g, u64 ncubes, const float* d_field, float iso,
     const u32 nc = static_cast<u32>(ncubes), nv32 = static_cast<u32>(nv);
     // pass 2: the map, the active cubes, and the vertices if they fit
     DevBuf active(pool), tofs(pool), tsums(pool);
-    const u64 tiles_v = (nv + 1 + SCAN_TILE - 1) / SCAN_TILE;
+    const u64 tiles_v = scan_tiles(nv + 1);
     if ((st = active.alloc(nv * sizeof(u32))) != PCPX_OK || (st = tofs.alloc((nv + 1) * sizeof(u64))) != PCPX_OK ||
         (st = tsums.alloc(std::max<u64>(tiles_v, 64) * sizeof(u64))) != PCPX_OK)
         return st;
@@ -653,7 +529,7 @@ int surface_nets_device(const float* d_field, const pcpx_grid3d& grid, float iso
     Events ev;
     if (times && (st = ev.create(4)) != PCPX_OK) return st;
     DevBuf vofs(pool), sums(pool), map(pool);
-    const u64 tiles_c = (ncubes + 1 + SCAN_TILE - 1) / SCAN_TILE;
+    const u64 tiles_c = scan_tiles(ncubes + 1);
     if ((st = vofs.alloc((ncubes + 1) * sizeof(u32))) != PCPX_OK || (st = map.alloc(ncubes * sizeof(u32))) != PCPX_OK ||
         (st = sums.alloc(std::max<u64>(tiles_c, 64) * sizeof(u64))) != PCPX_OK)
         return st;
@@ -766,7 +642,7 @@ int surface_nets_hint_device(const float* d_field, const pcpx_grid3d& grid, floa
         return PCPX_OK;
     };
     DevBuf vofs(pool), sums(pool), map(pool), active(pool), parent(pool), seed(pool), offs(pool);
-    const u64 tiles_c = (ncubes + 1 + SCAN_TILE - 1) / SCAN_TILE;
+    const u64 tiles_c = scan_tiles(ncubes + 1);
     if ((st = vofs.alloc((ncubes + 1) * sizeof(u32))) != PCPX_OK || (st = map.alloc(ncubes * sizeof(u32))) != PCPX_OK ||
         (st = sums.alloc(std::max<u64>(tiles_c, 64) * sizeof(u64))) != PCPX_OK || (st = seed.alloc(2 * sizeof(u64))) != PCPX_OK ||
         (st = offs.alloc(std::max<u64>(table, 1) * 3 * sizeof(int))) != PCPX_OK)

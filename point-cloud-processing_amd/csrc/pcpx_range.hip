@@ -2,28 +2,19 @@
 // walk as the kNN kernel (pcpx_device.h), one lane = one range, count, CSR fill or moments (normal, centroid, mean distance).
 #include "pcpx_device.h"
 #include "pcpx_eig3.h"
+#include "pcpx_scan.h"
 
-#ifndef PCPX_RANGE_DIRECT_LEAVES
-#define PCPX_RANGE_DIRECT_LEAVES 1
-#endif
-#ifndef PCPX_RANGE_PACKED_LEAVES
-#define PCPX_RANGE_PACKED_LEAVES 16  // count form: a leaf that at most this many lanes need is counted eight needing lanes x eight points at a time (0: off; <= 32: one 512-B row of LDS per wave)
-#endif
-
-// Wave priority by phase, as in k_knn (pcpx_query.hip): the dense leaf's 88 vector instructions run at a lower priority than the walk
-// and the packed leaves (2.238 -> 2.212 ms per 10 M counts; the dense leaf raised instead: 2.25)
-#ifndef PCPX_RANGE_PACKED_FILL
-#define PCPX_RANGE_PACKED_FILL 1  // the list form takes the packed leaf too (0: lane-per-range leaves, rounds 1-4)
-#endif
-#ifndef PCPX_RANGE_PRIO_BASE
-#define PCPX_RANGE_PRIO_BASE 1
-#endif
-#ifndef PCPX_RANGE_PRIO_DENSE
-#define PCPX_RANGE_PRIO_DENSE 0
-#endif
 namespace pcpx {
 
 namespace {
+
+// A leaf that at most this many lanes need is looked at eight needing lanes x eight points at a time (packed_leaf below), in
+// the count and the list form (lane-per-range leaves in the list form until round 4).  <= 32: one 512-B row of LDS per wave.
+constexpr u32 PACKED_LEAVES = 16;
+static_assert(PACKED_LEAVES <= 32, "one row of LDS per wave");
+// Wave priority by phase, as in k_knn (pcpx_query.hip): the dense leaf's 88 vector instructions run at a lower priority than the walk
+// and the packed leaves (2.238 -> 2.212 ms per 10 M counts; the dense leaf raised instead: 2.25)
+constexpr int PRIO_BASE = 1, PRIO_DENSE = 0;
 
 // ------------------------------------------------------------------------------------------------
 // sphere range: count / fill (include/pcp/octree/linked_octree_node.hpp:581-614 semantics:
@@ -56,26 +47,14 @@ __device__ __forceinline__ void range_group(const TreeView& t, const QueryView& 
     const u32 p = g * GROUP + lane;
     const u32 nq = SELF ? t.n : qv.nq;
     const bool valid = p < nq && (!SELF || p - qv.pos_lo < qv.pos_hi - qv.pos_lo);  // (self ranges: only the asked positions)
-    float qx = 0.f, qy = 0.f, qz = 0.f;
-    u32 row = 0;
-    if (valid) {
-        if (SELF) {
-            const Leaf& lf = t.leaves[p / LEAF];
-            qx = lf.x[p % LEAF];
-            qy = lf.y[p % LEAF];
-            qz = lf.z[p % LEAF];
-            row = lf.id[p % LEAF];
-        } else {
-            qx = qv.qx[p];
-            qy = qv.qy[p];
-            qz = qv.qz[p];
-            row = qv.row[p];
-        }
-    }
+    LaneQuery q{0.f, 0.f, 0.f, 0u};
+    if (valid) q = lane_query<SELF>(t, qv, p);
+    const float qx = q.x, qy = q.y, qz = q.z;
+    const u32 row = q.row;
     float r = radius;
     if (radii && valid) r = radii[row];
     const float r2 = valid ? r * r : -1.f;  // sphere.hpp:34 radius * radius in float; -1: idle lane
-    if (PCPX_RANGE_PRIO_BASE != 0) __builtin_amdgcn_s_setprio(PCPX_RANGE_PRIO_BASE);
+    __builtin_amdgcn_s_setprio(PRIO_BASE);
     u32 cnt = 0;
     u64 wpos = (FILL && valid) ? offsets[row] : 0;
     auto need = [&](const NodeBox& b) { return box_d2(b, qx, qy, qz) <= r2; };
@@ -98,7 +77,7 @@ __device__ __forceinline__ void range_group(const TreeView& t, const QueryView& 
             return;
         }
         if (!FILL) {
-            if (PCPX_RANGE_PRIO_DENSE != PCPX_RANGE_PRIO_BASE) __builtin_amdgcn_s_setprio(PCPX_RANGE_PRIO_DENSE);
+            __builtin_amdgcn_s_setprio(PRIO_DENSE);
             // count: the eight "inside" masks first (a scalar register pair each), then eight add-with-carry -- from
             // `cnt += in` hipcc pairs the points up as compare, select 0/1 under VCC, compare, add-with-carry, and the select
             // under a VCC that a compare has just written issues in 23 cycles on gfx950 (profiles/r03_valu_issue_rates.txt)
@@ -117,7 +96,7 @@ __device__ __forceinline__ void range_group(const TreeView& t, const QueryView& 
                 : "+v"(cnt), "=&s"(carry_out)
                 : "s"(inside[0]), "s"(inside[1]), "s"(inside[2]), "s"(inside[3]), "s"(inside[4]), "s"(inside[5]), "s"(inside[6]),
                   "s"(inside[7]));
-            if (PCPX_RANGE_PRIO_DENSE != PCPX_RANGE_PRIO_BASE) __builtin_amdgcn_s_setprio(PCPX_RANGE_PRIO_BASE);
+            __builtin_amdgcn_s_setprio(PRIO_BASE);
             return;
         }
 #pragma unroll
@@ -128,8 +107,7 @@ __device__ __forceinline__ void range_group(const TreeView& t, const QueryView& 
             cnt += in ? 1u : 0u;
         }
     };
-    auto leaf_points = [&](const u32 leaf) { leaf_record_points(load_const(t.leaves + leaf)); };
-    // A leaf that at most PCPX_RANGE_PACKED_LEAVES lanes need is counted EIGHT NEEDING LANES x EIGHT POINTS at a time (k_knn's
+    // A leaf that at most PACKED_LEAVES lanes need is counted EIGHT NEEDING LANES x EIGHT POINTS at a time (k_knn's
     // packed_leaf, pcpx_query.hip): the needing lanes publish {centre, r^2} in LDS in the order of their rank among the needing
     // lanes, lane 8 i + j forms the distance from the i-th published centre to point j, and a needing lane adds the number of set
     // bits of its own byte of the step's ballot -- ~12 vector instructions per eight needing lanes (+ 8 per leaf) against 88 per
@@ -140,8 +118,7 @@ __device__ __forceinline__ void range_group(const TreeView& t, const QueryView& 
     // and a lane whose point is inside writes the point's index at that place plus the number of set bits below its own in its
     // group's byte of the step's ballot -- the order of a list is the order of the lane-per-range form: walk order, then point
     // order inside a leaf.
-    constexpr bool packed_leaves = PCPX_RANGE_PACKED_LEAVES > 0 && (!FILL || PCPX_RANGE_PACKED_FILL) && MOM == 0;
-    static_assert(PCPX_RANGE_PACKED_LEAVES <= 32, "one row of LDS per wave");
+    constexpr bool packed_leaves = MOM == 0;
     auto packed_leaf = [&](const Leaf* record, const u64 who, const u32 how_many) {
         u32 lane_here = lane;
         asm volatile("" : "+v"(lane_here));  // (or what depends on the lane alone is kept in registers for the whole walk)
@@ -174,42 +151,10 @@ __device__ __forceinline__ void range_group(const TreeView& t, const QueryView& 
         if (mine) reinterpret_cast<float*>(pub + rank)[3] = -1.f;
         __builtin_amdgcn_wave_barrier();
     };
-    // the walk, with "is there another leaf" in the control flow rather than in a value (WalkerT::pop, pcpx_device.h)
-    WalkerT<true, packed_leaves> wk;
-    u32 nexp = 0;
-    if (wk.start(t, need, nexp))  // the root is the only unit
-        for (u32 leaf = 0; leaf < static_cast<u32>(UNIT_LEAVES) && leaf < t.nleaves; ++leaf) leaf_points(leaf);
-    // A last-level node looks at its needed leaves itself (WalkerT::leaves_of) instead of pushing and popping them: the four
-    // children written out, so that a child's record is an immediate offset from the node's first leaf and its lanes' ballot a
-    // register pair known at compile time (height 0 is popped only when the root's own children are leaves).
-    while (!wk.done()) {  // one pop per trip
-        u32 loc;
-        const int h = wk.pop(loc);
-        if (h > 1 || (!PCPX_RANGE_DIRECT_LEAVES && h == 1)) {
-            wk.expand(t, h, loc, need);
-        } else if (PCPX_RANGE_DIRECT_LEAVES || h == 1) {  // (no tree has depth 1 -- depth_of, pcpx_build.hip --: with last-level nodes looking
-                                                          //  at their leaves themselves no leaf is ever popped, and the case below is not compiled)
-            // (the children of a last-level node are UNITS of UNIT_LEAVES leaf records under one box)
-            const u32 needed = wk.leaves_of(t, loc, need);
-            const Leaf* records = t.leaves + (loc << LOGW) * UNIT_LEAVES;
-#pragma unroll
-            for (int c = 0; c < W; ++c) {
-                if ((needed >> c) & 1u) {
-                    u32 how_many = GROUP;
-                    if (packed_leaves) asm("s_bcnt1_i32_b64 %0, %1" : "=s"(how_many) : "s"(wk.leaf_need[c]) : "scc");
-#pragma unroll
-                    for (int r = 0; r < UNIT_LEAVES; ++r) {
-                        if (UNIT_LEAVES > 1 && ((loc << LOGW) + c) * UNIT_LEAVES + r >= t.nleaves) break;  // (the cloud's last unit may hold one leaf)
-                        if (packed_leaves && how_many <= static_cast<u32>(PCPX_RANGE_PACKED_LEAVES)) packed_leaf(records + c * UNIT_LEAVES + r, wk.leaf_need[c], how_many);
-                        else leaf_record_points(load_const(records + c * UNIT_LEAVES + r));
-                    }
-                }
-            }
-        } else {
-            wk.at_leaf(loc);
-            for (u32 leaf = loc * UNIT_LEAVES; leaf < (loc + 1u) * UNIT_LEAVES && leaf < t.nleaves; ++leaf) leaf_points(leaf);
-        }
-    }
+    walk_needed_leaves<packed_leaves>(t, need, [&](const u32, const Leaf* record, const u64 who, const u32 how_many) {
+        if (packed_leaves && how_many <= PACKED_LEAVES) packed_leaf(record, who, how_many);
+        else leaf_record_points(load_const(record));
+    });
     if constexpr (MOM != 0) {
         if (!valid) return;
         // epilogue: C = Q - S (S / n); n = 0 (an empty sphere) gives C = 0 -- the reference's empty scatter matrix -- and NaN for
@@ -329,13 +274,12 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void k_range_aabb(TreeView t,
     // at EIGHT NEEDING BOXES x EIGHT POINTS at a time, as in k_range (round 5; until then every visited leaf cost all 64 lanes its
     // eight containment tests).  The needing lanes publish their box -- and, list form, where their list stands -- by their rank
     // among the needing lanes; an unused slot holds an inverted box.
-    __shared__ float4 pub_lo_s[WAVES_PER_BLOCK][PCPX_RANGE_PACKED_LEAVES > 0 ? 32 : 1], pub_hi_s[WAVES_PER_BLOCK][PCPX_RANGE_PACKED_LEAVES > 0 ? 32 : 1];
-    __shared__ u64 pub_at_s[WAVES_PER_BLOCK][(PCPX_RANGE_PACKED_LEAVES > 0 && FILL) ? 32 : 1];
-    constexpr bool packed_leaves = PCPX_RANGE_PACKED_LEAVES > 0 && PCPX_RANGE_PACKED_FILL;
+    __shared__ float4 pub_lo_s[WAVES_PER_BLOCK][32], pub_hi_s[WAVES_PER_BLOCK][32];
+    __shared__ u64 pub_at_s[WAVES_PER_BLOCK][FILL ? 32 : 1];
     float4* const pub_lo = pub_lo_s[wave_in_block()];
     float4* const pub_hi = pub_hi_s[wave_in_block()];
     u64* const pub_at = pub_at_s[wave_in_block()];
-    if (packed_leaves && lane < 32u) {
+    if (lane < 32u) {
         pub_lo[lane] = make_float4(1.f, 1.f, 1.f, 0.f);
         pub_hi[lane] = make_float4(-1.f, -1.f, -1.f, 0.f);
     }
@@ -372,16 +316,17 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void k_range_aabb(TreeView t,
         }
         __builtin_amdgcn_wave_barrier();
     };
-    WalkerT<true, packed_leaves> wk;
+    // the walk of walk_needed_leaves (pcpx_device.h) with a last-level node's needed children in a scalar loop
+    WalkerT<true, true> wk;
     u32 nexp = 0;
     if (wk.start(t, need, nexp))
         for (u32 leaf = 0; leaf < static_cast<u32>(UNIT_LEAVES) && leaf < t.nleaves; ++leaf) leaf_points(leaf);
     while (!wk.done()) {  // one pop per trip: a node is expanded; a last-level node looks at its needed units itself
         u32 loc;
         const int h = wk.pop(loc);
-        if (h > 1 || (!packed_leaves && h == 1)) {
+        if (h > 1) {
             wk.expand(t, h, loc, need);
-        } else if (packed_leaves || h == 1) {  // (as in range_group: no leaf is ever popped)
+        } else {  // (no leaf is ever popped)
             u32 needed = wk.leaves_of(t, loc, need);
             // (one copy of the leaf forms, the needed children in a loop: written out four times two records they cost the count kernel
             //  133 saved scalar registers)
@@ -401,13 +346,10 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void k_range_aabb(TreeView t,
                 const u32 first = ((loc << LOGW) + c) * UNIT_LEAVES;
 #pragma unroll 1
                 for (u32 leaf = first; leaf < first + UNIT_LEAVES && leaf < t.nleaves; ++leaf) {
-                    if (how_many <= static_cast<u32>(PCPX_RANGE_PACKED_LEAVES)) packed_leaf(t.leaves + leaf, who, how_many);
+                    if (how_many <= PACKED_LEAVES) packed_leaf(t.leaves + leaf, who, how_many);
                     else leaf_points(leaf);
                 }
             }
-        } else {
-            wk.at_leaf(loc);
-            for (u32 leaf = loc * UNIT_LEAVES; leaf < (loc + 1u) * UNIT_LEAVES && leaf < t.nleaves; ++leaf) leaf_points(leaf);
         }
     }
     if (valid && !FILL) out_cnt[p] = cnt;
@@ -547,95 +489,11 @@ int launch_range_fill(Index& ix, const QueryView& qv, float radius, const float*
 }
 
 // ---- lists of every indexed point's range, device resident: counts by input row -> offsets (exclusive scan, 64-bit) -> fill ----
-namespace {
-constexpr u32 SCAN_TILE = 1024;
-// exclusive scan of n counts into 64-bit offsets (n + 1 of them): tile sums, their scan by one block, the tiles
-__global__ __launch_bounds__(256) void k_offsets_tile_sums(const u32* __restrict__ cnt, u32 n, u64* __restrict__ tile_sum)
-{
-    __shared__ u64 w[4];
-    const u32 base = blockIdx.x * SCAN_TILE;
-    u64 v = 0;
-#pragma unroll
-    for (u32 j = 0; j < SCAN_TILE / 256; ++j) {
-        const u32 i = base + j * 256 + threadIdx.x;
-        v += i < n ? cnt[i] : 0u;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    if ((threadIdx.x & 63u) == 0) w[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = w[0] + w[1] + w[2] + w[3];
-}
-__global__ __launch_bounds__(1024) void k_offsets_scan_sums(u64* __restrict__ tile_sum, u32 ntiles, u64* __restrict__ total_out)
-{
-    __shared__ u64 wsum[16];
-    __shared__ u64 carry_s;
-    const u32 t = threadIdx.x, lane = t & 63u, w = t >> 6;
-    if (t == 0) carry_s = 0;
-    __syncthreads();
-    for (u32 base = 0; base < ntiles; base += 1024) {
-        const u32 i = base + t;
-        const u64 v = i < ntiles ? tile_sum[i] : 0ull;
-        u64 incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const u64 up = __shfl_up(incl, off);
-            if (lane >= static_cast<u32>(off)) incl += up;
-        }
-        if (lane == 63) wsum[w] = incl;
-        __syncthreads();
-        u64 before = carry_s, total = 0;
-        for (u32 j = 0; j < 16; ++j) {
-            before += j < w ? wsum[j] : 0ull;
-            total += wsum[j];
-        }
-        if (i < ntiles) tile_sum[i] = before + incl - v;
-        __syncthreads();
-        if (t == 0) carry_s += total;
-        __syncthreads();
-    }
-    if (t == 0) *total_out = carry_s;
-}
-__global__ __launch_bounds__(256) void k_offsets_tiles(const u32* __restrict__ cnt, u32 n, const u64* __restrict__ tile_base, u64* __restrict__ offsets)
-{
-    __shared__ u32 w[4];
-    const u32 base = blockIdx.x * SCAN_TILE + threadIdx.x * (SCAN_TILE / 256);
-    u32 c[SCAN_TILE / 256], s = 0;
-#pragma unroll
-    for (u32 j = 0; j < SCAN_TILE / 256; ++j) {
-        c[j] = base + j < n ? cnt[base + j] : 0u;
-        s += c[j];
-    }
-    const u32 lane = threadIdx.x & 63u;
-    u32 incl = s;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const u32 up = __shfl_up(incl, off);
-        if (lane >= static_cast<u32>(off)) incl += up;
-    }
-    if (lane == 63) w[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    u32 before = 0;
-    for (u32 j = 0; j < (threadIdx.x >> 6); ++j) before += w[j];
-    u64 at = tile_base[blockIdx.x] + before + incl - s;
-#pragma unroll
-    for (u32 j = 0; j < SCAN_TILE / 256; ++j) {
-        if (base + j < n) offsets[base + j] = at;
-        at += c[j];
-    }
-}
-}  // namespace
-
 // d_offsets: n_rows + 1 entries (rows = input indices; a point that is not indexed has an empty list); d_total: one u64 (device).
 // d_cnt: n_rows counts (scratch of the caller); d_tile_sum: ceil(n_rows / 1024) + 1 u64 (scratch).
 int launch_range_offsets(Index& ix, const u32* d_cnt, u64 n_rows, u64* d_tile_sum, u64* d_offsets)
 {
-    if (n_rows == 0) return PCPX_OK;
-    const u32 n = static_cast<u32>(n_rows), ntiles = (n + SCAN_TILE - 1) / SCAN_TILE;
-    k_offsets_tile_sums<<<ntiles, 256, 0, ix.stream>>>(d_cnt, n, d_tile_sum);
-    k_offsets_scan_sums<<<1, 1024, 0, ix.stream>>>(d_tile_sum, ntiles, d_offsets + n_rows);
-    k_offsets_tiles<<<ntiles, 256, 0, ix.stream>>>(d_cnt, n, d_tile_sum, d_offsets);
-    return check_hip(hipGetLastError(), "range offset kernels", __FILE__, __LINE__);
+    return exclusive_scan<u64>(ArrayRows<u32>{d_cnt}, n_rows, d_tile_sum, d_offsets, d_offsets + n_rows, ix.stream);  // 32-bit counts, 64-bit offsets
 }
 int launch_range_fill_self(Index& ix, u64 group_first, u64 group_count, float radius, const u64* d_offsets, u32* d_out_idx)
 {

@@ -27,6 +27,7 @@
 // and nothing uses atomics, so two runs give the same bits.  The leaves of a level come out in ascending b and the levels
 // in order, so the output is the reference's queue order without a sort.
 #include "pcpx_internal.h"
+#include "pcpx_scan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -40,7 +41,6 @@ constexpr int HS_ITEMS = 8;
 constexpr u32 HS_CHUNK = HS_WAVE * HS_ITEMS;  // points per chunk
 constexpr int HS_BLOCK = 256;
 constexpr int HS_WPB = HS_BLOCK / HS_WAVE;
-constexpr int HS_SCAN_THREADS = 256, HS_SCAN_ITEMS = 8, HS_SCAN_TILE = HS_SCAN_THREADS * HS_SCAN_ITEMS;
 
 // per active cluster of the level being processed
 struct ClusterState {
@@ -463,81 +463,6 @@ __global__ __launch_bounds__(HS_BLOCK) void k_hs_gather(const float* __restrict_
     if (out_idx) out_idx[i] = idx[i];
 }
 
-// ---- exclusive scan of u64, in place, over n entries (the last entry is 0 and receives the total) --------------------------
-
-__device__ u64 hs_block_scan(u64 v, u64* lds, u64& total)
-{
-    const int t = threadIdx.x;
-    lds[t] = v;
-    __syncthreads();
-    for (int off = 1; off < HS_SCAN_THREADS; off <<= 1) {
-        const u64 add = t >= off ? lds[t - off] : 0ull;
-        __syncthreads();
-        lds[t] += add;
-        __syncthreads();
-    }
-    const u64 incl = lds[t];
-    total = lds[HS_SCAN_THREADS - 1];
-    __syncthreads();
-    return incl - v;
-}
-
-__global__ __launch_bounds__(HS_SCAN_THREADS) void k_hs_scan_reduce(const u64* __restrict__ a, u64 n, u64* __restrict__ sums)
-{
-    __shared__ u64 lds[HS_SCAN_THREADS];
-    const u64 base = static_cast<u64>(blockIdx.x) * HS_SCAN_TILE;
-    u64 s = 0;
-    for (int r = 0; r < HS_SCAN_ITEMS; ++r) {
-        const u64 e = base + static_cast<u64>(r) * HS_SCAN_THREADS + threadIdx.x;
-        if (e < n) s += a[e];
-    }
-    u64 total;
-    (void)hs_block_scan(s, lds, total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(HS_SCAN_THREADS) void k_hs_scan_sums(u64* __restrict__ sums, u64 ntiles)
-{
-    __shared__ u64 lds[HS_SCAN_THREADS];
-    u64 carry = 0;
-    for (u64 base = 0; base < ntiles; base += HS_SCAN_THREADS) {
-        const u64 e = base + threadIdx.x;
-        const u64 v = e < ntiles ? sums[e] : 0ull;
-        u64 total;
-        const u64 ex = hs_block_scan(v, lds, total);
-        if (e < ntiles) sums[e] = carry + ex;
-        carry += total;
-    }
-}
-
-__global__ __launch_bounds__(HS_SCAN_THREADS) void k_hs_scan_apply(u64* __restrict__ a, u64 n, const u64* __restrict__ sums)
-{
-    __shared__ u64 lds[HS_SCAN_THREADS];
-    const u64 base = static_cast<u64>(blockIdx.x) * HS_SCAN_TILE + static_cast<u64>(threadIdx.x) * HS_SCAN_ITEMS;
-    u64 mine[HS_SCAN_ITEMS], s = 0;
-#pragma unroll
-    for (int r = 0; r < HS_SCAN_ITEMS; ++r) {  // thread t owns items [t*ITEMS, t*ITEMS + ITEMS) of the tile
-        mine[r] = s;
-        s += base + r < n ? a[base + r] : 0ull;
-    }
-    u64 total;
-    const u64 ex = hs_block_scan(s, lds, total) + sums[blockIdx.x];
-#pragma unroll
-    for (int r = 0; r < HS_SCAN_ITEMS; ++r)
-        if (base + r < n) a[base + r] = ex + mine[r];
-}
-
-int scan_u64(u64* d_a, u64 n, u64* d_sums, hipStream_t s)
-{
-    const u64 tiles = (n + HS_SCAN_TILE - 1) / HS_SCAN_TILE;
-    if (tiles == 0) return PCPX_OK;
-    k_hs_scan_reduce<<<static_cast<u32>(tiles), HS_SCAN_THREADS, 0, s>>>(d_a, n, d_sums);
-    k_hs_scan_sums<<<1, HS_SCAN_THREADS, 0, s>>>(d_sums, tiles);
-    k_hs_scan_apply<<<static_cast<u32>(tiles), HS_SCAN_THREADS, 0, s>>>(d_a, n, d_sums);
-    PCPX_HIP(hipGetLastError());
-    return PCPX_OK;
-}
-
 // the wave kernels stride over their chunks / clusters: 64 K blocks of four waves fill the card many times over
 u32 wave_blocks(u64 waves)
 {
@@ -568,7 +493,7 @@ int hierarchy_device(const float* d_xyz, u64 n, u64 cluster_size, double var_max
     const double vmax = static_cast<double>(static_cast<float>(var_max));  // the reference compares with (float)var_max
     const u32 n32 = static_cast<u32>(n);
     const u64 max_chunks = n + (n + HS_CHUNK - 1) / HS_CHUNK;  // sum over clusters of ceil(L / CHUNK) <= n / CHUNK + clusters
-    const u64 scan_tiles = (n + 1 + HS_SCAN_TILE - 1) / HS_SCAN_TILE;
+    const u64 tiles = scan_tiles(n + 1);
     DevBuf rec0(pool), rec1(pool), cl0(pool), cl1(pool), ch00(pool), ch01(pool), stb(pool), pkb(pool), sums(pool), part(pool), cnt(pool),
         bd2(pool), bidx(pool), outi(pool), ctlb(pool);
     int st;
@@ -576,7 +501,7 @@ int hierarchy_device(const float* d_xyz, u64 n, u64 cluster_size, double var_max
         (st = cl0.alloc(n * sizeof(uint2))) != PCPX_OK || (st = cl1.alloc(n * sizeof(uint2))) != PCPX_OK ||
         (st = ch00.alloc((n + 1) * sizeof(u64))) != PCPX_OK || (st = ch01.alloc((n + 1) * sizeof(u64))) != PCPX_OK ||
         (st = stb.alloc(n * sizeof(ClusterState))) != PCPX_OK || (st = pkb.alloc((n + 1) * sizeof(u64))) != PCPX_OK ||
-        (st = sums.alloc(std::max<u64>(scan_tiles, 64) * sizeof(u64))) != PCPX_OK || (st = part.alloc(max_chunks * 6 * sizeof(double))) != PCPX_OK ||
+        (st = sums.alloc(std::max<u64>(tiles, 64) * sizeof(u64))) != PCPX_OK || (st = part.alloc(max_chunks * 6 * sizeof(double))) != PCPX_OK ||
         (st = cnt.alloc(max_chunks * sizeof(u32))) != PCPX_OK || (st = bd2.alloc(max_chunks * sizeof(double))) != PCPX_OK ||
         (st = bidx.alloc(max_chunks * sizeof(u32))) != PCPX_OK || (st = outi.alloc(n * sizeof(u32))) != PCPX_OK ||
         (st = ctlb.alloc(sizeof(Ctl))) != PCPX_OK) {
@@ -625,14 +550,14 @@ int hierarchy_device(const float* d_xyz, u64 n, u64 cluster_size, double var_max
         k_hs_resolve<<<wave_blocks(K), HS_BLOCK, 0, s>>>(cl[cur], ch0[cur], K32, cnt.as<u32>(), bd2.as<double>(), bidx.as<u32>(), cs, pk);
         PCPX_HIP(hipGetLastError());
         PCPX_HIP(hipMemsetAsync(pk + K, 0, sizeof(u64), s));
-        if ((st = scan_u64(pk, K + 1, sums.as<u64>(), s)) != PCPX_OK) return st;
+        if ((st = exclusive_scan_in_place<u64>(pk, K + 1, sums.as<u64>(), s)) != PCPX_OK) return st;
         // the next level has at most min(2K, n) clusters; their chunk counts, zero beyond, scanned with one entry more
         const u64 m = std::min<u64>(2 * K, n) + 1;
         PCPX_HIP(hipMemsetAsync(ch0[nxt], 0, m * sizeof(u64), s));
         k_hs_emit<<<thread_blocks(K), HS_BLOCK, 0, s>>>(cl[cur], K32, cs, pk, ctl, outi.as<u32>(), cl[nxt], ch0[nxt]);
         k_hs_scatter<<<wave_blocks(C), HS_BLOCK, 0, s>>>(rec[cur], cl[cur], ch0[cur], K32, C, cs, cnt.as<u32>(), rec[nxt]);
         PCPX_HIP(hipGetLastError());
-        if ((st = scan_u64(ch0[nxt], m, sums.as<u64>(), s)) != PCPX_OK) return st;
+        if ((st = exclusive_scan_in_place<u64>(ch0[nxt], m, sums.as<u64>(), s)) != PCPX_OK) return st;
         k_hs_tail<<<1, 1, 0, s>>>(K32, pk, ch0[nxt], ctl);
         PCPX_HIP(hipGetLastError());
         PCPX_HIP(hipMemcpyAsync(&h, ctl, sizeof(Ctl), hipMemcpyDeviceToHost, s));

@@ -65,13 +65,14 @@ def test_cluster_null_handle_is_refused(lib):
 
 @pytest.mark.timeout(600)
 def test_cluster_kernels_use_no_scratch():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), "pcpx_cluster.hip", "k_cluster"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), "pcpx_cluster.hip", "k_"],
                          capture_output=True, text=True, timeout=580, check=True).stdout
-    rows = dict((m[0], [int(v) for v in m[1:]]) for m in re.findall(
-        r"(k_cluster_\w+)\(.*?vgpr\s+(\d+) sgpr\s+(\d+) sspill\s+(\d+) vspill\s+(\d+) scratch\s+(\d+)", out))
+    rows = dict((m[0], [int(v) for v in m[1:]]) for m in re.findall(  # (the scan's kernels are the shared templates of pcpx_scan.h)
+        r"(k_(?:cluster|scan)_\w+)(?:<[^\n]*?>)?\(.*?vgpr\s+(\d+) sgpr\s+(\d+) sspill\s+(\d+) vspill\s+(\d+) scratch\s+(\d+)", out))
     assert sorted(rows) == sorted(["k_cluster_init", "k_cluster_hook", "k_cluster_flatten", "k_cluster_label", "k_cluster_border",
-                                   "k_cluster_rows", "k_cluster_tile_sums", "k_cluster_scan_sums", "k_cluster_ranks",
+                                   "k_cluster_rows", "k_scan_tile_sums", "k_scan_sums", "k_scan_tiles",
                                    "k_cluster_compact"]), out
+    assert len(out.strip().splitlines()) == len(rows), out  # (every kernel of the file is among them)
     for name, (vgpr, _sgpr, sspill, vspill, scratch) in rows.items():
         assert scratch == 0 and vspill == 0 and sspill == 0, (name, out)
     for name in ("k_cluster_hook", "k_cluster_border"):  # the two forms of the sphere walk
