@@ -16,16 +16,6 @@ namespace pcpx {
 
 namespace {
 
-#ifndef PCPX_BUILD_ADAPTIVE_MARGIN
-#define PCPX_BUILD_ADAPTIVE_MARGIN 6  // PCPX_BUILD_COARSE_ORDER: bits of curve resolution kept beyond log2 of a top-digit bucket's size
-#endif
-#ifndef PCPX_BUILD_FINISH
-#define PCPX_BUILD_FINISH 1  // 1: the sort stops after two bucketed passes where that leaves short runs and k_finish orders them in LDS (round 5); 0: every pass
-#endif
-#ifndef PCPX_BUILD_RECORDS
-#define PCPX_BUILD_RECORDS 1  // 1: the sort's first pass moves a {x, y, z, id} record per point into its top-digit bucket and the leaf
-                              // fill gathers from there; 0: the leaf fill gathers the coordinates from the input-order copy
-#endif
 constexpr size_t SCALARS = 32;  // u32 words of Index::d_scalars: [0, 6) encoded box, [6] points outside the grid, [7] sort failure, [8, 14) box,
                                 //   [16, 24) buckets whose runs the finish kernel could not order (REDO_WORD0), [24, 32) the buckets to sort fully (FORCE_WORD0)
 constexpr u32 REDO_WORD0 = 16, FORCE_WORD0 = 24, LOW_TILES_WORD = 15;  // ([15]: tiles of the sort's lowest pass, see sort_for_build)
@@ -240,20 +230,6 @@ __device__ __forceinline__ float leaf_max(float v)
     return v;
 }
 
-// ... and over the UNIT_POINTS lanes of a unit (two leaves: one more step, the other half of the row of sixteen)
-__device__ __forceinline__ float unit_min(float v)
-{
-    v = leaf_min(v);
-    if (UNIT_LEAVES == 2) v = fminf(v, __uint_as_float(__builtin_amdgcn_mov_dpp(__float_as_uint(v), 0x128, 0xF, 0xF, true)));  // row_ror:8
-    return v;
-}
-__device__ __forceinline__ float unit_max(float v)
-{
-    v = leaf_max(v);
-    if (UNIT_LEAVES == 2) v = fmaxf(v, __uint_as_float(__builtin_amdgcn_mov_dpp(__float_as_uint(v), 0x128, 0xF, 0xF, true)));
-    return v;
-}
-
 // node i of a level = union of its 4 children (padding children are skipped; no real child: a padding node)
 __device__ __forceinline__ NodeBox union_of_children(const NodeBox* __restrict__ child4)
 {
@@ -302,14 +278,10 @@ struct TreeShape {
 // points, 256 positions apart, so that four gathers are in flight per lane.
 // Blocks are dealt so that each XCD works through one contiguous eighth of the sorted order.
 constexpr int FILL_BLOCK = 256;
-#ifndef PCPX_FILL_PER_THREAD
-#define PCPX_FILL_PER_THREAD 4
-#endif
-constexpr int FILL_PER_THREAD = PCPX_FILL_PER_THREAD;
+constexpr int FILL_PER_THREAD = 4;
 constexpr int FILL_SLOTS = FILL_BLOCK * FILL_PER_THREAD;  // 1024
-constexpr int FILL_LEAVES = FILL_SLOTS / LEAF;            // 128
-constexpr int FILL_UNITS = FILL_LEAVES / UNIT_LEAVES;     // bottom-level boxes a block makes
-static_assert(FILL_UNITS >= 64, "a block makes the three levels above its units");
+constexpr int FILL_LEAVES = FILL_SLOTS / LEAF;            // 128: the leaf boxes a block makes
+static_assert(FILL_LEAVES >= 64, "a block makes the three levels above its leaves");
 
 // The tree's shape from the number of inserted points, on the device: the kernels below read that number where the build left it
 // (Index::d_scalars: input points minus the points outside the grid), so the host need not wait for it between the sort and them.
@@ -327,20 +299,19 @@ __host__ __device__ inline int depth_of(u32 nleaves)
     while ((1ull << (2 * d)) < nleaves) ++d;
     return d == 1 ? 2 : d;
 }
-// (TreeShape::nleaves is the number of nodes of the bottom level: UNITS of UNIT_LEAVES leaves)
 __host__ __device__ inline TreeShape shape_of(u32 nvalid)
 {
-    const u32 nunits = (nvalid + UNIT_POINTS - 1) / UNIT_POINTS;
-    return TreeShape{nunits, depth_of(nunits)};
+    const u32 nleaves = (nvalid + LEAF - 1) / LEAF;
+    return TreeShape{nleaves, depth_of(nleaves)};
 }
 // blocks of k_finish a tree of this shape needs: its leaf slots, and the (padding) nodes of the three levels above that a block owns
 __host__ __device__ inline u32 finish_blocks(const TreeShape& ts)
 {
     if (ts.nleaves == 0) return 0;
-    const u32 nslots = ts.nwrite(ts.depth) * UNIT_POINTS;
+    const u32 nslots = ts.nwrite(ts.depth) * LEAF;
     u32 fblocks = (nslots + FILL_SLOTS - 1) / FILL_SLOTS;
-    for (int j = 1; j <= 3 && j <= ts.depth; ++j) {  // a block owns FILL_UNITS >> 2j nodes of level depth - j
-        const u32 per_block = static_cast<u32>(FILL_UNITS) >> (2 * j);
+    for (int j = 1; j <= 3 && j <= ts.depth; ++j) {  // a block owns FILL_LEAVES >> 2j nodes of level depth - j
+        const u32 per_block = static_cast<u32>(FILL_LEAVES) >> (2 * j);
         const u32 need = (ts.nwrite(ts.depth - j) + per_block - 1) / per_block;
         if (need > fblocks) fblocks = need;
     }
@@ -368,12 +339,12 @@ struct FinishArgs {
     u32* redo;                     // bitmap, 8 words
 };
 
-__global__ __launch_bounds__(FILL_BLOCK) void k_finish(const float4* __restrict__ rec, const float* __restrict__ xyz, FinishArgs fa, int idx_bits,
+__global__ __launch_bounds__(FILL_BLOCK) void k_finish(const float4* __restrict__ rec, FinishArgs fa, int idx_bits,
                                                        BuildCount bc, Leaf* __restrict__ leaves, u32* __restrict__ perm, NodeBox* __restrict__ nodes)
 {
-    __shared__ __attribute__((aligned(16))) NodeBox lvl0[FILL_UNITS];      // unit boxes of the block
-    __shared__ __attribute__((aligned(16))) NodeBox lvl1[FILL_UNITS / 4];
-    __shared__ __attribute__((aligned(16))) NodeBox lvl2[FILL_UNITS / 16];
+    __shared__ __attribute__((aligned(16))) NodeBox lvl0[FILL_LEAVES];     // leaf boxes of the block
+    __shared__ __attribute__((aligned(16))) NodeBox lvl1[FILL_LEAVES / 4];
+    __shared__ __attribute__((aligned(16))) NodeBox lvl2[FILL_LEAVES / 16];
     // (the window of words and its flags are dead when the leaf records are staged: one piece of LDS for both -- 21 KB per block, seven
     //  blocks per CU, as before the window was there)
     union alignas(16) Piece {
@@ -501,18 +472,11 @@ __global__ __launch_bounds__(FILL_BLOCK) void k_finish(const float4* __restrict_
     u32 id[FILL_PER_THREAD];
 #pragma unroll
     for (int u = 0; u < FILL_PER_THREAD; ++u) {
-        if (rec) {
-            const float4 r = rec[at[u]];
-            x[u] = r.x;
-            y[u] = r.y;
-            z[u] = r.z;
-            id[u] = __float_as_uint(r.w);
-        } else {
-            id[u] = static_cast<u32>(at[u]);
-            x[u] = xyz[3 * at[u]];
-            y[u] = xyz[3 * at[u] + 1];
-            z[u] = xyz[3 * at[u] + 2];
-        }
+        const float4 r = rec[at[u]];
+        x[u] = r.x;
+        y[u] = r.y;
+        z[u] = r.z;
+        id[u] = __float_as_uint(r.w);
     }
     const float inf = std::numeric_limits<float>::infinity(), nan = __builtin_nanf("");
     const u32 lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
@@ -535,21 +499,21 @@ __global__ __launch_bounds__(FILL_BLOCK) void k_finish(const float4* __restrict_
         const u32 wave_leaf0 = (p - lane) / LEAF;  // first leaf of the wave's 64 points
         const uint4 piece = *reinterpret_cast<const uint4*>(stage + 4 * lane);
         if (wave_leaf0 + (lane >> 3) < nleaves_real) reinterpret_cast<uint4*>(leaves + wave_leaf0)[lane] = piece;
-        // (every lane of the group of UNIT_POINTS lanes takes part in the reduction, whatever it holds)
-        const float lx = unit_min(live ? x[u] : inf), ly = unit_min(live ? y[u] : inf), lz = unit_min(live ? z[u] : inf);
-        const float hx = unit_max(live ? x[u] : -inf), hy = unit_max(live ? y[u] : -inf), hz = unit_max(live ? z[u] : -inf);
-        if ((p % UNIT_POINTS) == 0) {
+        // (every lane of the leaf's LEAF lanes takes part in the reduction, whatever it holds)
+        const float lx = leaf_min(live ? x[u] : inf), ly = leaf_min(live ? y[u] : inf), lz = leaf_min(live ? z[u] : inf);
+        const float hx = leaf_max(live ? x[u] : -inf), hy = leaf_max(live ? y[u] : -inf), hz = leaf_max(live ? z[u] : -inf);
+        if ((p % LEAF) == 0) {
             NodeBox nb = padding_node();
-            if (p / UNIT_POINTS < ts.nleaves) {
+            if (p / LEAF < ts.nleaves) {
                 nb.set(lx, ly, lz, hx, hy, hz);
                 nb.poison = 0.f;
             }
-            lvl0[(threadIdx.x + u * FILL_BLOCK) / UNIT_POINTS] = nb;
+            lvl0[(threadIdx.x + u * FILL_BLOCK) / LEAF] = nb;
         }
     }
     // the block's leaf boxes, then the three levels above (32, 8 and 2 nodes per 128 leaves): every level leaves LDS as
     // 16-byte pieces of one contiguous run of the heap
-    const u32 l0 = vb * FILL_UNITS;  // the block's first unit
+    const u32 l0 = vb * FILL_LEAVES;  // the block's first leaf
     auto store_level = [&](const NodeBox* boxes, u32 count, int level, u32 first) {
         const u32 nw = ts.nwrite(level);
         uint4* dst = reinterpret_cast<uint4*>(nodes + TreeShape::level_start(level) + first);
@@ -557,20 +521,20 @@ __global__ __launch_bounds__(FILL_BLOCK) void k_finish(const float4* __restrict_
             if (first + (t >> 1) < nw) dst[t] = reinterpret_cast<const uint4*>(boxes)[t];
     };
     __syncthreads();
-    store_level(lvl0, FILL_UNITS, ts.depth, l0);
-    if (ts.depth >= 1 && threadIdx.x < FILL_UNITS / 4) {
+    store_level(lvl0, FILL_LEAVES, ts.depth, l0);
+    if (ts.depth >= 1 && threadIdx.x < FILL_LEAVES / 4) {
         const u32 i = (l0 >> 2) + threadIdx.x;
         lvl1[threadIdx.x] = i < ts.nreal(ts.depth - 1) ? union_of_children(lvl0 + 4 * threadIdx.x) : padding_node();
     }
     __syncthreads();
-    if (ts.depth >= 1) store_level(lvl1, FILL_UNITS / 4, ts.depth - 1, l0 >> 2);
-    if (ts.depth >= 2 && threadIdx.x < FILL_UNITS / 16) {
+    if (ts.depth >= 1) store_level(lvl1, FILL_LEAVES / 4, ts.depth - 1, l0 >> 2);
+    if (ts.depth >= 2 && threadIdx.x < FILL_LEAVES / 16) {
         const u32 i = (l0 >> 4) + threadIdx.x;
         lvl2[threadIdx.x] = i < ts.nreal(ts.depth - 2) ? union_of_children(lvl1 + 4 * threadIdx.x) : padding_node();
     }
     __syncthreads();
-    if (ts.depth >= 2) store_level(lvl2, FILL_UNITS / 16, ts.depth - 2, l0 >> 4);
-    if (ts.depth >= 3 && threadIdx.x < FILL_UNITS / 64) {
+    if (ts.depth >= 2) store_level(lvl2, FILL_LEAVES / 16, ts.depth - 2, l0 >> 4);
+    if (ts.depth >= 3 && threadIdx.x < FILL_LEAVES / 64) {
         const u32 i = (l0 >> 6) + threadIdx.x;
         if (i < ts.nwrite(ts.depth - 3))
             nodes[TreeShape::level_start(ts.depth - 3) + i] = i < ts.nreal(ts.depth - 3) ? union_of_children(lvl2 + 4 * threadIdx.x) : padding_node();
@@ -838,10 +802,8 @@ int build_tree_from_sorted(Index& ix, u32 n_at_most, bool count_on_device)
     if (ts.nleaves == 0) return PCPX_OK;
     const BuildCount bc{count_on_device ? ix.d_scalars : nullptr, static_cast<u32>(ix.n_in), n_at_most};
     const u32 fgrid = (finish_blocks(ts) + 7u) & ~7u;
-    const bool from_rec = PCPX_BUILD_RECORDS || ix.shard.on;
     const FinishArgs fa{ix.finish_words, ix.d_codes[1], ix.finish_first_pass, SORT_FIRST_BIT, ix.d_scalars + REDO_WORD0};
-    k_finish<<<fgrid, FILL_BLOCK, 0, s>>>(from_rec ? reinterpret_cast<const float4*>(ix.d_rec) : nullptr, ix.d_xyz, fa, ix.idx_bits, bc, ix.d_leaves,
-                                          ix.d_perm, ix.d_nodes);
+    k_finish<<<fgrid, FILL_BLOCK, 0, s>>>(reinterpret_cast<const float4*>(ix.d_rec), fa, ix.idx_bits, bc, ix.d_leaves, ix.d_perm, ix.d_nodes);
     int stage = 0;
     for (int c = ts.depth - 3; c > 0; c -= 5, ++stage) {
         const int levels = c < 5 ? c : 5;
@@ -892,7 +854,7 @@ int build_index(Index& ix, const float* d_xyz_src, u64 n, const pcpx_build_param
     (void)coarse;  // (round 5: every build sorts only as finely as its buckets ask for, and exactly; the flag is accepted and changes nothing)
     for (int attempt = 0;; ++attempt) {
         if (n > 0) {
-            if ((st = sort_for_build(ix, ix.d_codes[0], n, PCPX_BUILD_RECORDS ? d_xyz_src : nullptr, nullptr, sort_tile_hist_buffer(ix.d_sort_tmp, n))) != PCPX_OK) return st;
+            if ((st = sort_for_build(ix, ix.d_codes[0], n, d_xyz_src, nullptr, sort_tile_hist_buffer(ix.d_sort_tmp, n))) != PCPX_OK) return st;
             if ((st = build_tree_from_sorted(ix, static_cast<u32>(n), true)) != PCPX_OK) return st;
         }
         u32 hb[SCALARS - 6];
@@ -943,7 +905,7 @@ int sort_for_build(Index& ix, const u64* d_words, u64 n, const float* d_xyz_src,
     pl.idx_bits = ix.idx_bits;
     pl.tile_hist_ready = tile_hist_ready;
     pl.failed_flag = ix.d_scalars + 7;
-    pl.finish = PCPX_BUILD_FINISH != 0;
+    pl.finish = true;
     pl.force_full = any_forced ? ix.d_scalars + FORCE_WORD0 : nullptr;
     pl.finish_out = &fo;
     pl.low_pass_tiles_hint = ix.low_pass_tiles;

@@ -15,10 +15,7 @@
 namespace pcpx {
 namespace {
 
-#ifndef PCPX_WPB
-#define PCPX_WPB 1
-#endif
-constexpr int WAVES_PER_BLOCK = PCPX_WPB;  // 1: a finished wave frees its LDS at once (no intra-block tail)
+constexpr int WAVES_PER_BLOCK = 1;  // 1: a finished wave frees its LDS at once (no intra-block tail)
 
 __device__ __forceinline__ u32 wave_in_block() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
 
@@ -226,7 +223,7 @@ using Walker = WalkerT<true, false>;
 // control flow rather than in a value (WalkerT::pop).  A last-level node looks at its needed leaves itself (leaves_of)
 // instead of pushing and popping them: the four children written out, so that a child's record is an immediate offset from
 // the node's first leaf and its lanes' ballot a register pair known at compile time.  No tree has depth 1 (depth_of,
-// pcpx_build.hip), so no leaf is ever popped; the children of a last-level node are UNITS of UNIT_LEAVES records under one box.
+// pcpx_build.hip), so no leaf is ever popped.
 // BOUNDED: only the leaves below leaf_end.  The walk is depth first in curve order, so the first node that starts at or
 // beyond leaf_end ends it.
 // (k_range_aabb, pcpx_range.hip, keeps a second form with the children in a scalar loop: 133 scalar registers fewer there.)
@@ -235,30 +232,24 @@ __device__ __forceinline__ void walk_needed_leaves(const TreeView& t, Need&& nee
 {
     WalkerT<true, KEEP> wk;
     u32 nexp = 0;
-    if (wk.start(t, need, nexp))  // the root is the only unit
-        for (u32 leaf = 0; leaf < static_cast<u32>(UNIT_LEAVES) && leaf < t.nleaves && (!BOUNDED || leaf < leaf_end); ++leaf)
-            leaf_fn(leaf, t.leaves + leaf, ~0ull, static_cast<u32>(GROUP));
+    if (wk.start(t, need, nexp) && t.nleaves != 0u && (!BOUNDED || leaf_end != 0u))  // the root is the only leaf
+        leaf_fn(0u, t.leaves, ~0ull, static_cast<u32>(GROUP));
     while (!wk.done()) {  // one pop per trip
         u32 loc;
         const int h = wk.pop(loc);
-        if (BOUNDED && (static_cast<u64>(loc) << (LOGW * h)) * UNIT_LEAVES >= leaf_end) break;  // this node and all that are pending lie later
+        if (BOUNDED && (static_cast<u64>(loc) << (LOGW * h)) >= leaf_end) break;  // this node and all that are pending lie later
         if (h > 1) {
             wk.expand(t, h, loc, need);
         } else {
             const u32 needed = wk.leaves_of(t, loc, need);
-            const Leaf* records = t.leaves + (loc << LOGW) * UNIT_LEAVES;
+            const Leaf* records = t.leaves + (loc << LOGW);
 #pragma unroll
             for (int c = 0; c < W; ++c) {
                 if ((needed >> c) & 1u) {
                     u32 how_many = GROUP;
                     if (KEEP) asm("s_bcnt1_i32_b64 %0, %1" : "=s"(how_many) : "s"(wk.leaf_need[c]) : "scc");
-#pragma unroll
-                    for (int r = 0; r < UNIT_LEAVES; ++r) {
-                        const u32 leaf = ((loc << LOGW) + c) * UNIT_LEAVES + r;
-                        if (UNIT_LEAVES > 1 && leaf >= t.nleaves) break;  // (the cloud's last unit may hold one leaf)
-                        if (BOUNDED && leaf >= leaf_end) break;
-                        leaf_fn(leaf, records + c * UNIT_LEAVES + r, KEEP ? wk.leaf_need[c] : ~0ull, how_many);
-                    }
+                    const u32 leaf = (loc << LOGW) + c;
+                    if (!BOUNDED || leaf < leaf_end) leaf_fn(leaf, records + c, KEEP ? wk.leaf_need[c] : ~0ull, how_many);
                 }
             }
         }

@@ -94,21 +94,7 @@ __global__ __launch_bounds__(256) void k_take_rows(const float* __restrict__ xyz
 // Acc::CAP = entries per lane between two flushes, per loop, by measurement: a long list keeps more lanes busy when it
 // is worked off (the normal loop's Jacobian, ~400 instructions per neighbour: 13.0 ms at 32 entries, 8.0 ms at 64), a
 // short one leaves LDS for more waves (everything else: within 3 % between 32 and 48).
-#ifndef PCPX_CAP_POINTS
-#define PCPX_CAP_POINTS 40
-#endif
-#ifndef PCPX_CAP_NORMALS
-#define PCPX_CAP_NORMALS 64
-#endif
-#ifndef PCPX_CAP_DENSITY
-#define PCPX_CAP_DENSITY 40
-#endif
-#ifndef PCPX_CAP_MEDIAN
-#define PCPX_CAP_MEDIAN 40
-#endif
-#ifndef PCPX_CAP_REPULSION
-#define PCPX_CAP_REPULSION 40
-#endif
+constexpr int CAP_POINTS = 40, CAP_NORMALS = 64, CAP_DENSITY = 40, CAP_MEDIAN = 40, CAP_REPULSION = 40;
 typedef unsigned short list_entry;
 constexpr u32 LIST_SPAN = 65536u / LEAF;  // leaves one epoch of the lists can address
 
@@ -140,34 +126,34 @@ __device__ __forceinline__ void visit_group(const TreeView& t, const QueryView& 
     acc.begin(qx, qy, qz, p, valid);
     auto need = [&](const NodeBox& b) { return box_d2(b, qx, qy, qz) <= r2; };
     Walker wk;
-    u32 unit = 0, nexp = 0, cnt = 0;  // (the walk yields UNITS of the tree's bottom level: UNIT_LEAVES consecutive leaf records each)
+    u32 leaf = 0, nexp = 0, cnt = 0;
     bool more = wk.start(t, need, nexp);
-    if (!more) more = wk.next(t, need, unit, nexp);
-    u32 base_leaf = unit * UNIT_LEAVES;  // wave-uniform: the epoch of the lists
+    if (!more) more = wk.next(t, need, leaf, nexp);
+    u32 base_leaf = leaf;  // wave-uniform: the epoch of the lists
     while (more) {
-      for (u32 leaf = unit * UNIT_LEAVES; leaf < (unit + 1u) * UNIT_LEAVES && leaf < t.nleaves; ++leaf) {
-        if (leaf - base_leaf >= LIST_SPAN) {  // offsets from here on would not fit an entry
-            flush_list(list, base_leaf * LEAF, lane, cnt, qx, qy, qz, acc);
-            cnt = 0;
-            base_leaf = leaf;
-        }
-        const Leaf lf = load_const(t.leaves + leaf);
-        const u32 rel = (leaf - base_leaf) * LEAF;
+        if (leaf < t.nleaves) {
+            if (leaf - base_leaf >= LIST_SPAN) {  // offsets from here on would not fit an entry
+                flush_list(list, base_leaf * LEAF, lane, cnt, qx, qy, qz, acc);
+                cnt = 0;
+                base_leaf = leaf;
+            }
+            const Leaf lf = load_const(t.leaves + leaf);
+            const u32 rel = (leaf - base_leaf) * LEAF;
 #pragma unroll
-        for (int j = 0; j < LEAF; ++j) {
-            const float dx = lf.x[j] - qx, dy = lf.y[j] - qy, dz = lf.z[j] - qz;
-            if (sq3(dx, dy, dz) <= r2) {  // = common::squared_distance(centre, point) <= r*r, norm.hpp:102-112
-                list[cnt * GROUP + lane] = static_cast<list_entry>(rel + j);
-                ++cnt;
+            for (int j = 0; j < LEAF; ++j) {
+                const float dx = lf.x[j] - qx, dy = lf.y[j] - qy, dz = lf.z[j] - qz;
+                if (sq3(dx, dy, dz) <= r2) {  // = common::squared_distance(centre, point) <= r*r, norm.hpp:102-112
+                    list[cnt * GROUP + lane] = static_cast<list_entry>(rel + j);
+                    ++cnt;
+                }
+            }
+            if (any_lane(cnt > Acc::CAP - LEAF)) {  // the next leaf could overflow a column
+                flush_list(list, base_leaf * LEAF, lane, cnt, qx, qy, qz, acc);
+                cnt = 0;
+                base_leaf = leaf;
             }
         }
-        if (any_lane(cnt > Acc::CAP - LEAF)) {  // the next leaf could overflow a column
-            flush_list(list, base_leaf * LEAF, lane, cnt, qx, qy, qz, acc);
-            cnt = 0;
-            base_leaf = leaf;
-        }
-      }
-        more = wk.next(t, need, unit, nexp);
+        more = wk.next(t, need, leaf, nexp);
     }
     flush_list(list, base_leaf * LEAF, lane, cnt, qx, qy, qz, acc);
     if (valid) acc.finish(row);
@@ -202,7 +188,7 @@ __device__ __forceinline__ float norm3(float x, float y, float z)
 // bilateral::detail::compute_pi (bilateral_filter.hpp:47-101)
 struct BilateralPoints {
     using Rec = Rec8;
-    static constexpr int CAP = PCPX_CAP_POINTS;
+    static constexpr int CAP = CAP_POINTS;
     const Rec8* recs;  // point + its normal
     Gauss f, g;
     float* out;  // n_in x 3
@@ -253,7 +239,7 @@ __device__ __forceinline__ void normalized3(float x, float y, float z, float& ox
 // bilateral::detail::compute_ni (bilateral_filter.hpp:103-269): the Jacobian of the filter at s applied to s's normal
 struct BilateralNormals {
     using Rec = Rec8;
-    static constexpr int CAP = PCPX_CAP_NORMALS;
+    static constexpr int CAP = CAP_NORMALS;
     const Rec8* recs;  // point + its normal
     Gauss f, g;
     float* out;  // n_in x 3
@@ -342,7 +328,7 @@ __device__ __forceinline__ bool near_eq(float a, float b) { return fabsf(a - b) 
 // compute_vj / compute_wi (wlop.hpp:29-105): 1 + sum of theta(r2) over the range, points equal to the centre skipped
 struct WlopDensity {
     using Rec = Rec4;
-    static constexpr int CAP = PCPX_CAP_DENSITY;
+    static constexpr int CAP = CAP_DENSITY;
     const Rec4* recs;
     float h16;   // (h * h) / 16
     float* out;  // n_in
@@ -363,7 +349,7 @@ struct WlopDensity {
 // solve_first_energy_median (wlop.hpp:107-170): centres are the samples x, the tree holds the input cloud and its v_j
 struct WlopMedian {
     using Rec = Rec4;
-    static constexpr int CAP = PCPX_CAP_MEDIAN;
+    static constexpr int CAP = CAP_MEDIAN;
     const Rec4* recs;  // cloud point + its v_j
     float h16;
     float* out;  // I x 3
@@ -399,7 +385,7 @@ struct WlopMedian {
 // tree are both the samples x
 struct WlopRepulsion {
     using Rec = Rec4;
-    static constexpr int CAP = PCPX_CAP_REPULSION;
+    static constexpr int CAP = CAP_REPULSION;
     const Rec4* recs;  // sample + its w_i
     float h16, mu;
     const float* median;  // I x 3

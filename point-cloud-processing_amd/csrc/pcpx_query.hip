@@ -27,7 +27,9 @@
 //   * PCA normals are fused into the same kernel: no neighbour list round trip through HBM.
 //   * Rows go to the query's input index, or (KnnOutputs::by_position, self queries) to its curve position: slices of
 //     the curve order are then contiguous in every output array (pcpx_normals_knn_self_curve_order).
-// The measurements behind every tuning constant below are in profiles/experiments/README.md.
+// The measurements behind every tuning constant below are in profiles/experiments/README.md.  So are the forms that were built,
+// measured and removed -- the node-level packed form, the last round's groups in pieces, two leaf records under one box, overrides of
+// the per-KCAP seed range and cap: their code is in commit b37c5b7.
 //
 // Arithmetic follows the reference exactly: d = p - q, dx*dx + dy*dy + dz*dz in float32 without
 // FMA contraction (include/pcp/common/norm.hpp:102-112), eps-box exclusion
@@ -136,91 +138,46 @@ __device__ __forceinline__ void bitonic_merge(u64 (&a)[N])
 
 // Rows of the per-lane append buffer.  A leaf may append LEAF keys, so a compaction runs whenever a
 // lane holds more than BUF - LEAF keys; fewer rows = less LDS per wave = more resident waves.
-#ifndef PCPX_BUF16
-#define PCPX_BUF16 10  // 10 rows x 512 B = 5 KB per wave = 7 waves/SIMD
-#endif
-#ifndef PCPX_BUF32
-#define PCPX_BUF32 14  // (+ 2 rows of LDS that only the epilogue uses: lds_rows)
-#endif
-#ifndef PCPX_COMPACT_BY8
-#define PCPX_COMPACT_BY8 1     // compaction in chunks of 8 keys
-#endif
-// (the multi-pass kernels -- k > 32 -- keep the 16-key compaction and the C++ accept path with its trash row)
-#ifndef PCPX_BUF8
-#define PCPX_BUF8 10   // k <= 8: 10 rows x 512 B = 5 KB per wave, 8 waves/SIMD
-#endif
-#ifndef PCPX_ASM_ACCEPT
-#define PCPX_ASM_ACCEPT 1
-#endif
-#ifndef PCPX_SEED_DIRECT
-#define PCPX_SEED_DIRECT 8  // largest KCAP whose seed leaves skip the append buffer (k <= 16 / 32: scratch in the seed phase)
-#endif
-#ifndef PCPX_PACKED_LEAVES
-#define PCPX_PACKED_LEAVES 24  // a walk leaf that 2 ... this many lanes need is looked at eight needing lanes x eight points at a time (0: off)
-#endif
-#ifndef PCPX_PACKED_NODE
-#define PCPX_PACKED_NODE 0  // a LAST-LEVEL node that at most this many lanes need is looked at TWO NEEDING LANES x ITS 32 POINTS at a time, its four
-                             // leaf boxes never tested (0: off; <= PCPX_PACKED_LEAVES: the publish row's slots)
-#endif
-#ifndef PCPX_PACKED_NODE_KCAP
-#define PCPX_PACKED_NODE_KCAP 16  // largest KCAP whose kernel has the node form (the k <= 32 kernel fills its buffer without the optimistic form's check: PCPX_PACKED_FREE)
-#endif
-#ifndef PCPX_PACKED_FREE
-#define PCPX_PACKED_FREE 3  // k <= 16 kernel: free rows every needing lane has when a packed leaf starts (0: LEAF of them, like the other forms -- no key can then find its column full).  The k <= 32 kernel always waits for LEAF rows: its fold is twice the network, and what the optimistic fill loses there it does not win back (measured)
-#endif
+constexpr int BUF8 = 10;   // k <= 8: 10 rows x 512 B = 5 KB per wave, 8 waves/SIMD
+constexpr int BUF16 = 10;  // 10 rows x 512 B = 5 KB per wave = 7 waves/SIMD
+constexpr int BUF32 = 14;  // (+ 2 rows of LDS that only the epilogue uses: lds_rows)
+constexpr int SEED_DIRECT = 8;     // largest KCAP whose seed leaves skip the append buffer (k <= 16 / 32: scratch in the seed phase)
+constexpr int PACKED_LEAVES = 24;  // a walk leaf that 2 ... this many lanes need is looked at eight needing lanes x eight points at a time
+constexpr int PACKED_FREE16 = 3;   // k <= 16 kernel: free rows every needing lane has when a packed leaf starts.  The k <= 32 kernel always waits for LEAF rows, like the other forms -- no key can then find its column full: its fold is twice the network, and what the optimistic fill loses there it does not win back (measured)
 // Wave priorities (s_setprio) by phase of a group.  A fold is ~130 vector instructions back to back that wait for nothing; the
 // walk and the leaf forms are short runs of arithmetic between loads whose round trips are what a wave's time is made of.  With the
 // fold at a LOWER priority than the rest, a SIMD's issue slots go first to the waves that are about to issue a load, and the folds
 // fill what is left: +2 % at k = 15 (uniform and clustered), +5 % at k = 32 (four waves per SIMD: fewer to hide a round trip
 // behind), +1 % at k = 8.  The other way round (fold raised) -3 ... -6 %; a lower priority for the epilogue or the dense leaves
 // as well: nothing, or -1 % at k = 8; base 3 instead of 1: the same (only the order matters).  profiles/experiments/README.md.
-#ifndef PCPX_PRIO_BASE
-#define PCPX_PRIO_BASE 1
-#endif
-#ifndef PCPX_PRIO_FOLD
-#define PCPX_PRIO_FOLD 0
-#endif
-#ifndef PCPX_PRIO_PACKED
-#define PCPX_PRIO_PACKED 2  // the packed leaf (three dependent LDS round trips on top of its loads) one step above the rest: +0.8 % (five rounds)
-#endif
-#ifndef PCPX_PRIO_WALK
-#define PCPX_PRIO_WALK PCPX_PRIO_BASE
-#endif
-#ifndef PCPX_PRIO_DENSE
-#define PCPX_PRIO_DENSE PCPX_PRIO_BASE
-#endif
-#ifndef PCPX_PRIO_EPI
-#define PCPX_PRIO_EPI PCPX_PRIO_BASE
-#endif
-#ifndef PCPX_KNN_WPB16
-#define PCPX_KNN_WPB16 4  // waves per workgroup of the k <= 16 kernel: its 11 rows x 512 B per wave fill the LDS allocation granule
-                          // (1280 B) only in fours -- 7 waves per SIMD need <= 5851 B per wave
-#endif
-#ifndef PCPX_COMPACT_TIER4
-#define PCPX_COMPACT_TIER4 8  // largest KCAP whose compaction has a four-key tier (k <= 8: +2 %; k <= 16: the branch costs the kernel
-                              // scratch at 7 waves per SIMD and nothing at 6; k <= 32: no difference)
-#endif
-#ifndef PCPX_BY8_K32
-#define PCPX_BY8_K32 1  // the chunk-of-8 compaction (with its PAD invariant established) for the single-pass k <= 32 kernel too
-#endif
-// rows of LDS per wave: the C++ accept path (multi-pass kernels only) stores rejected keys to a trash row, row BUF;
-// the exec-masked path stores nothing for a rejected candidate
+constexpr int PRIO_BASE = 1;
+constexpr int PRIO_FOLD = 0;
+constexpr int PRIO_PACKED = 2;  // the packed leaf (three dependent LDS round trips on top of its loads) one step above the rest: +0.8 % (five rounds)
+constexpr int KNN_WPB16 = 4;  // waves per workgroup of the k <= 16 kernel: its 11 rows x 512 B per wave fill the LDS allocation granule
+                              // (1280 B) only in fours -- 7 waves per SIMD need <= 5851 B per wave
+constexpr int COMPACT_TIER4 = 8;  // largest KCAP whose compaction has a four-key tier (k <= 8: +2 %; k <= 16: the branch costs the kernel
+                                  // scratch at 7 waves per SIMD and nothing at 6; k <= 32: no difference)
+// What selects a path, each said once.  MULTI = a pass of the multi-pass search (k > 32); EPS_EACH = the per-candidate eps-box test
+// (eps test mode 2, or an eps that is large against the spacing of the points: launch_knn_t).
+//   exec-masked accept (append_if*): the single-pass kernels.  The multi-pass kernels keep the C++ accept path, which stores a
+//   rejected key to a trash row (row BUF); the exec-masked path stores nothing for a rejected candidate.
+constexpr bool exec_masked_accept(bool multi) { return !multi; }
+//   chunk-of-8 compaction (compact_by8, with its PAD invariant established): the single-pass kernels; multi-pass: the 16-key compact().
+constexpr bool chunked_compaction(bool multi) { return !multi; }
+//   deferred eps-box test (EpsFilter): lives in the chunk-of-8 compaction -- compact() has none.
+constexpr bool deferred_eps(bool multi, bool eps_each) { return chunked_compaction(multi) && !eps_each; }
+//   The packed leaf form (knn_group: packed_leaf) publishes the needing lanes' queries in rows of their own behind the buffer: 20 B per
+//   needing lane.  The kernels that have it: single-pass, k <= 16 and k <= 32 (the k <= 8 kernel has no LDS to spare at 8 waves per SIMD).
+__host__ __device__ constexpr int pack_rows(bool multi, int kcap) { return (!multi && kcap >= 16) ? (PACKED_LEAVES * 20 + 511) / 512 : 0; }
+// rows of LDS per wave: the buffer, the multi-pass kernels' trash row, the packed leaf's publish rows
 // (single-pass kernels: at least kcap / 2 rows -- after the search the column holds the row's kcap sorted positions, two per row)
-// The packed leaf form (knn_group: packed_leaf) publishes the needing lanes' queries in rows of their own behind the buffer: 20 B per
-// needing lane.  The kernels that have it: single-pass, k <= 16 and k <= 32 (the k <= 8 kernel has no LDS to spare at 8 waves per SIMD).
-__host__ __device__ constexpr int pack_rows(bool multi, int kcap)
-{
-    return (PCPX_PACKED_LEAVES > 0 && PCPX_ASM_ACCEPT && !multi && kcap >= 16) ? (PCPX_PACKED_LEAVES * 20 + 511) / 512 : 0;
-}
 __host__ __device__ constexpr int lds_rows(int buf, bool multi, int kcap = 0)
 {
-    return (buf + ((multi || !PCPX_ASM_ACCEPT) ? 1 : 0) + pack_rows(multi, kcap)) > kcap / 2
-               ? (buf + ((multi || !PCPX_ASM_ACCEPT) ? 1 : 0) + pack_rows(multi, kcap))
-               : kcap / 2;
+    return (buf + (multi ? 1 : 0) + pack_rows(multi, kcap)) > kcap / 2 ? (buf + (multi ? 1 : 0) + pack_rows(multi, kcap)) : kcap / 2;
 }
 // waves per workgroup (every wave works alone; the workgroup only shares an LDS allocation)
-__host__ __device__ constexpr int knn_wpb(int kcap, bool multi) { return (!multi && kcap == 16 && pack_rows(multi, kcap) > 0) ? PCPX_KNN_WPB16 : WAVES_PER_BLOCK; }
-__host__ __device__ constexpr int buf_rows(int kcap) { return kcap <= 8 ? PCPX_BUF8 : kcap <= 16 ? PCPX_BUF16 : PCPX_BUF32; }
+__host__ __device__ constexpr int knn_wpb(int kcap, bool multi) { return (!multi && kcap == 16 && pack_rows(multi, kcap) > 0) ? KNN_WPB16 : WAVES_PER_BLOCK; }
+__host__ __device__ constexpr int buf_rows(int kcap) { return kcap <= 8 ? BUF8 : kcap <= 16 ? BUF16 : BUF32; }
 
 // Fold this lane's buffered keys (cnt <= BUF <= 16) into its sorted best-list.  All LDS traffic is
 // unconditional (stale slots are masked to PAD_KEY in registers): no exec games.  The new keys are sorted
@@ -264,10 +221,6 @@ __device__ __forceinline__ void static_for(F&& f)
 // first ones.  Self queries meet exactly one such key per lane (the query point itself), so two or three of a group's
 // ~44 compactions take the slow path below, against a v_max3 + v_cmpx for each of its ~780 candidates.  A key that fails
 // never reaches best[]: tau only ever comes from neighbours.  `on` is wave-uniform (launch-uniform, in fact).
-#ifndef PCPX_DEFER_EPS
-#define PCPX_DEFER_EPS 1
-#endif
-static_assert(!PCPX_DEFER_EPS || (PCPX_COMPACT_BY8 * PCPX_BY8_K32 != 0), "the deferred eps-box test lives in the chunk-of-8 compaction: compact() has none");
 struct EpsFilter {
     bool on;
     float thr, eps, qx, qy, qz;
@@ -310,7 +263,7 @@ template <int KCAP, int BUF, int NZ>
 __device__ __forceinline__ void compact_by8(u64 (&best)[KCAP], u64* __restrict__ col, int& cnt, const EpsFilter& f)
 {
     static_assert(BUF >= 8 && BUF <= 16 && KCAP >= 8, "rows");
-    if (KCAP <= PCPX_COMPACT_TIER4 && !any_lane(cnt > 4)) {  // about half of the compactions of a walk: four rows, five compare-exchanges
+    if (KCAP <= COMPACT_TIER4 && !any_lane(cnt > 4)) {  // about half of the compactions of a walk: four rows, five compare-exchanges
         u64 nw[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) nw[j] = col[j * 64];
@@ -487,28 +440,15 @@ __device__ __forceinline__ void append_if_shell(float d2, float tau, float lo, f
 // ------------------------------------------------------------------------------------------------
 // kNN (+ fused PCA normals)
 // ------------------------------------------------------------------------------------------------
-#ifndef PCPX_MINW8
-#define PCPX_MINW8 8   // k <= 8 kernel: 63 VGPRs = 8 waves/SIMD
-#endif
-#ifndef PCPX_MINW32
-#define PCPX_MINW32 4  // k <= 32 kernel: <= 128 VGPRs = 4 waves/SIMD
-#endif
-#ifndef PCPX_MINW
-#define PCPX_MINW 7  // k <= 16 kernel: <= 72 VGPRs = 7 waves/SIMD
-#endif
-// PCPX_CAP_MULT x the median of the finite seeded taus of a sample of the wave's valid lanes (every fourth lane:
+constexpr int MINW8 = 8;   // k <= 8 kernel: 63 VGPRs = 8 waves/SIMD
+constexpr int MINW16 = 7;  // k <= 16 kernel: <= 72 VGPRs = 7 waves/SIMD
+constexpr int MINW32 = 4;  // k <= 32 kernel: <= 128 VGPRs = 4 waves/SIMD
+// cap_mult x the median of the finite seeded taus of a sample of the wave's valid lanes (every fourth lane:
 // 16 readlanes; inf if no lane has a finite tau): rank every sampled value by counting, pick the middle one.
 // The cap only steers the work, never the result (a lane that fails the cap goes round again).
-#ifdef PCPX_CAP_MULT
-template <int KCAP>
-constexpr float cap_mult() { return PCPX_CAP_MULT; }
-#else
 template <int KCAP>
 constexpr float cap_mult() { return KCAP <= 8 ? 1.375f : KCAP <= 16 ? 1.25f : 1.125f; }
-#endif
-#ifndef PCPX_CAP_GROW
-#define PCPX_CAP_GROW 4.f  // radius^2 growth per further round
-#endif
+constexpr float CAP_GROW = 4.f;  // radius^2 growth per further round
 template <int KCAP>
 __device__ __forceinline__ float wave_radius_cap(float tau, bool valid, u32 lane)
 {
@@ -603,7 +543,7 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
     //  per kernel and parked in spilled scalar registers)
     TreeView t = tree;
     asm volatile("" : "+s"(t.depth), "+s"(t.nodes));
-    if (PCPX_PRIO_BASE != PCPX_PRIO_EPI || PCPX_PRIO_BASE != PCPX_PRIO_FOLD || PCPX_PRIO_BASE != PCPX_PRIO_DENSE) __builtin_amdgcn_s_setprio(PCPX_PRIO_BASE);
+    __builtin_amdgcn_s_setprio(PRIO_BASE);
     // the cold arguments (KnnArgs), as this group's start sees them: dead before the search begins
     const knn_args_ptr ka = knn_args_here();
     const u32 k_arg = ka->k;
@@ -638,9 +578,9 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
     const u32 nq = SELF ? t.n : ka->qv.nq;
     // (self queries: only the positions [pos_lo, pos_hi) the caller asked for -- a slice that starts or ends inside a group)
     // (`part` = 0: the whole group; 1 ... 8: only its lanes 8 (part - 1) ... 8 part - 1 -- an eighth of a LONG group, whose other eighths
-    //  other waves answer at the same time; 9 ... 12: a quarter, 13 / 14: a half -- the groups of a launch's last, partly filled round:
-    //  order_entries.  From p, which is opaque per group: from `lane` it is one more value kept from group to group.)
-    const bool mine_of_part = part <= 8u ? ((p >> 3) & 7u) + 1u == part : part <= 12u ? ((p >> 4) & 3u) + 9u == part : ((p >> 5) & 1u) + 13u == part;
+    //  other waves answer at the same time: order_entries.  From p, which is opaque per group: from `lane` it is one more value kept
+    //  from group to group.)
+    const bool mine_of_part = ((p >> 3) & 7u) + 1u == part;
     const bool valid = p < nq && (!SELF || p - pos_lo < pos_hi - pos_lo) && (part == 0u || mine_of_part);
     float qx = 0.f, qy = 0.f, qz = 0.f;
     if (valid) {
@@ -677,18 +617,18 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
     bool active = valid;             // lanes still searching (the second walk round keeps only the failed ones)
     int cnt = 0;
     const u32 col_addr = lds_address(col);  // byte address of row 0 of this lane's column
-    u32 wa = col_addr;                      // byte address of the next free row (PCPX_ASM_ACCEPT)
+    u32 wa = col_addr;                      // byte address of the next free row (exec-masked accept)
     // a lane's column starts at lds_row0 + 8 * lane (< lds_row0 + 512), so "more than c keys buffered" is a comparison of
     // wa with a wave-uniform bound: no per-lane threshold register
     const u32 lds_row0 = __builtin_amdgcn_readfirstlane(col_addr) - 8u * __builtin_amdgcn_readfirstlane(lane);
     const u32 wa_full = lds_row0 + (static_cast<u32>(BUF - LEAF + 1) << 9);  // wa >= this: a leaf might not fit any more
     const u32 wa_end = lds_row0 + (static_cast<u32>(BUF) << 9);               // a key address >= this: beyond the column's last row
-    constexpr int packed_free = KCAP <= 16 ? PCPX_PACKED_FREE : 0;  // (see PCPX_PACKED_FREE)
+    constexpr int packed_free = KCAP <= 16 ? PACKED_FREE16 : 0;  // (see PACKED_FREE16)
     const u32 wa_packed_full = packed_free > 0 ? lds_row0 + (static_cast<u32>(BUF - packed_free + 1) << 9) : wa_full;
 
     auto need = [&](const NodeBox& b) { return box_d2(b, qx, qy, qz) <= tau; };
     // single-pass kernels: the eps-box test waits for the compaction, unless the launcher picked the EPS_EACH form (launch_knn_t)
-    const EpsFilter eps_filter{PCPX_ASM_ACCEPT && !MULTI && !EPS_EACH, eps_thr, eps, qx, qy, qz, t.leaves};
+    const EpsFilter eps_filter{deferred_eps(MULTI, EPS_EACH), eps_thr, eps, qx, qy, qz, t.leaves};
 
     // ---- seed range: the 64-point chunk at the group's own curve position ----
     u32 s0, s1;
@@ -698,12 +638,7 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
     if (s0 > s1) s0 = s1;
     // leaves before and after the group's own chunk that are also processed before the walk: they are curve neighbours the walk
     // would visit anyway, and seeing them first tightens tau sooner.  How many pays depends on k.
-#ifdef PCPX_SEED_EXTRA
-    constexpr u32 seed_extra = PCPX_SEED_EXTRA;
-#else
     constexpr u32 seed_extra = KCAP <= 8 ? 0u : KCAP <= 16 ? 2u : 4u;
-#endif
-    static_assert(seed_extra % UNIT_LEAVES == 0 && LEAVES_PER_GROUP % UNIT_LEAVES == 0, "the seed range is whole units of the tree's bottom level");
     if (seed_extra > 0) {
         s0 = s0 > seed_extra ? s0 - seed_extra : 0u;
         s1 = s1 + seed_extra < t.nleaves ? s1 + seed_extra : t.nleaves;
@@ -723,21 +658,21 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
     // covers the whole cloud.
     float cap = inf;       // wave-uniform; inf = no cap
     float lo_d2 = -1.f;    // wave-uniform; later rounds accept only d2 > lo_d2
-    constexpr bool fast = PCPX_ASM_ACCEPT && !MULTI;  // keeps only the write address `wa`; the other accept paths only `cnt`
+    constexpr bool fast = exec_masked_accept(MULTI);  // keeps only the write address `wa`; the other accept paths only `cnt`
 
     // (diagnostic build: the dense forms count a key where it is accepted, the packed form where it is folded -- fold() then counts EVERY
     //  key of the column, so with packed leaves in the kernel the dense forms' own counts are left out: `count_at_accept`)
-    constexpr bool packed_keys_counted_at_folds = STATS && pack_rows(MULTI, KCAP) > 0 && PCPX_ASM_ACCEPT && !MULTI && !EPS_EACH;
+    constexpr bool packed_keys_counted_at_folds = STATS && pack_rows(MULTI, KCAP) > 0 && !EPS_EACH;
     constexpr bool count_at_accept = STATS && !packed_keys_counted_at_folds;
     // fold the buffered keys into the best-list (one copy of the selection network per call site)
     auto fold = [&](bool in_seed_phase) {
         if (STATS) tc_mark = __builtin_amdgcn_s_memtime();
         if (fast) cnt = static_cast<int>((wa - col_addr) >> 9);
         if (STATS && packed_keys_counted_at_folds) st_app += static_cast<u32>(cnt);  // (the packed leaves' keys: see the leaf loop)
-        if (PCPX_PRIO_FOLD != PCPX_PRIO_BASE) __builtin_amdgcn_s_setprio(PCPX_PRIO_FOLD);
-        if (PCPX_COMPACT_BY8 && (KCAP <= 16 || (PCPX_BY8_K32 && !MULTI))) compact_by8<KCAP, BUF, NZ>(best, col, cnt, eps_filter);
+        __builtin_amdgcn_s_setprio(PRIO_FOLD);
+        if (chunked_compaction(MULTI)) compact_by8<KCAP, BUF, NZ>(best, col, cnt, eps_filter);
         else compact<KCAP, BUF>(best, col, cnt);
-        if (PCPX_PRIO_FOLD != PCPX_PRIO_BASE) __builtin_amdgcn_s_setprio(PCPX_PRIO_BASE);
+        __builtin_amdgcn_s_setprio(PRIO_BASE);
         float nt = __uint_as_float(static_cast<u32>(best[KCAP - 1] >> 32));
         tau = active ? fminf(nt, cap) : -1.f;
         if (STATS) tau = fminf(tau, tau_known);
@@ -766,7 +701,6 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
         }
         const Leaf lf = load_const(t.leaves + leaf);  // (a vector-memory fetch of the record measured the same)
         const u32 posbase = leaf * LEAF;
-        if (PCPX_PRIO_DENSE != PCPX_PRIO_BASE) __builtin_amdgcn_s_setprio(PCPX_PRIO_DENSE);
         // copies of the candidate loop, switched per leaf (hipcc otherwise re-tests the mode per point)
         if (fast && eps_filter.on && !shell && !STATS) {
             u32 posv = posbase;
@@ -832,7 +766,6 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
                 if (count_at_accept) st_app += acc ? 1u : 0u;
             }
         }
-        if (PCPX_PRIO_DENSE != PCPX_PRIO_BASE) __builtin_amdgcn_s_setprio(PCPX_PRIO_BASE);
         if (STATS) {
             asm volatile("" ::"v"(wa), "v"(cnt));
             tc_leaf += __builtin_amdgcn_s_memtime() - tc_mark;
@@ -844,7 +777,7 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
     // skip the append buffer: built in registers, sorted, filtered for the eps-box and merged like a chunk of the buffer
     // (the same best-list as accepting them one by one: a key beyond tau falls off its end).  Not for the cloud's last leaf
     // (its padding slots are NaN, which the compare-exchange network cannot carry) and not in the per-candidate eps form.
-    constexpr bool direct_seeds = KCAP <= PCPX_SEED_DIRECT && fast && !EPS_EACH && !STATS && PCPX_COMPACT_BY8 && (KCAP <= 16 || PCPX_BY8_K32);
+    constexpr bool direct_seeds = KCAP <= SEED_DIRECT && chunked_compaction(MULTI) && !EPS_EACH && !STATS;
     auto seed_direct = [&](const u32 leaf) {
         const Leaf lf = load_const(t.leaves + leaf);
         const u32 posbase = leaf * LEAF;
@@ -882,7 +815,7 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
     // ---- walk rounds ----
     constexpr bool packed_leaves = pack_rows(MULTI, KCAP) > 0 && fast && !EPS_EACH;  // (wants the lanes that need each leaf: WalkerT's KEEP)
     WalkerT<(KCAP > 8), packed_leaves> wk;
-    // A leaf of the walk that at most PCPX_PACKED_LEAVES lanes need (three quarters of the walk's leaves: the lane-per-query form
+    // A leaf of the walk that at most PACKED_LEAVES lanes need (three quarters of the walk's leaves: the lane-per-query form
     // computes 512 distances there of which 8 ... 192 matter) is looked at EIGHT NEEDING LANES x EIGHT POINTS at a time: the
     // needing lanes publish {query, tau} and their write address in LDS in the order of their rank (v_mbcnt of the need mask);
     // lane 8 i + j then forms the distance from the i-th published query to point j of the leaf, and a lane whose point is
@@ -894,37 +827,22 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
     // Slots that hold no query hold tau = -1 (k_knn sets them so, a needing lane sets its slot back when the leaf is done): the
     // lanes of a step beyond the leaf's needing lanes compare against that and take nothing -- no lane mask per step, and the
     // scalar unit is as loaded as the vector units here (profiles/experiments/README.md, round 4).
-    // PCPX_PACKED_FREE > 0: the buffer is filled OPTIMISTICALLY -- a leaf is started as soon as every needing lane has that many
+    // packed_free > 0 (PACKED_FREE16): the buffer is filled OPTIMISTICALLY -- a leaf is started as soon as every needing lane has that many
     // free rows (the other forms want LEAF = 8: any lane may take every point; in the walk a lane takes one key of a leaf it
     // needs, rarely three, and waiting for eight free rows of ten meant a fold -- the whole selection network, for all 64
     // lanes -- per 19 keys of the WAVE).  A key whose add comes back with an address beyond the column goes to a spare word of
     // the publish row instead; the needing lane sees from the address it reads back that keys were lost, takes its column back
     // to where it was before the leaf (the rows written since hold PAD_KEY again), and the leaf is looked at once more for
     // those lanes after a fold.  Returns the lanes that want that (0: done).
-    // The same for a whole LAST-LEVEL NODE that few lanes need (`sh` = 5: lane 32 i + j forms the distance from the i-th published query
-    // to point j of the node's 32, two needing lanes a step; `sh` = 3: one leaf, as above): the node's four leaf boxes are then never
-    // tested -- d2 <= tau is the test that counts -- and its leaves cost one publish and read-back instead of one each.  A leaf of the
-    // node that is in the seed range (seen already), or beyond the cloud's last, shows NaN to every query.
-    auto packed_leaf = [&](const u32 leaf, const u64 who, const u32 how_many, const u32 sh) -> u64 {
-        float4* const pub_q = reinterpret_cast<float4*>(pub);                     // [PCPX_PACKED_LEAVES] {qx, qy, qz, tau}
-        u32* const pub_wa = reinterpret_cast<u32*>(pub) + 4 * PCPX_PACKED_LEAVES;  // [PCPX_PACKED_LEAVES] next free row of the column
-        if (PCPX_PRIO_PACKED != PCPX_PRIO_BASE) __builtin_amdgcn_s_setprio(PCPX_PRIO_PACKED);
+    auto packed_leaf = [&](const u32 leaf, const u64 who, const u32 how_many) -> u64 {
+        float4* const pub_q = reinterpret_cast<float4*>(pub);                     // [PACKED_LEAVES] {qx, qy, qz, tau}
+        u32* const pub_wa = reinterpret_cast<u32*>(pub) + 4 * PACKED_LEAVES;  // [PACKED_LEAVES] next free row of the column
+        __builtin_amdgcn_s_setprio(PRIO_PACKED);
         u32 lane_here = lane;
         asm volatile("" : "+v"(lane_here));  // (or everything below that depends on the lane alone sits in registers from group to group)
-        const u32 j = PCPX_PACKED_NODE > 0 ? lane_here & ((1u << sh) - 1u) : lane_here & 7u, i = PCPX_PACKED_NODE > 0 ? lane_here >> sh : lane_here >> 3;
-        float cx, cy, cz;
-        if (PCPX_PACKED_NODE > 0) {
-            const u32 lf = leaf + (j >> 3);
-            const bool shown = lf < t.nleaves && lf - s0 >= s1 - s0;
-            cx = std::numeric_limits<float>::quiet_NaN(), cy = 0.f, cz = 0.f;
-            if (shown) {
-                const float* rec = reinterpret_cast<const float*>(t.leaves + lf);
-                cx = rec[j & 7u], cy = rec[LEAF + (j & 7u)], cz = rec[2 * LEAF + (j & 7u)];
-            }
-        } else {
-            const float* rec = reinterpret_cast<const float*>(t.leaves + leaf);
-            cx = rec[j], cy = rec[LEAF + j], cz = rec[2 * LEAF + j];
-        }
+        const u32 j = lane_here & 7u, i = lane_here >> 3;
+        const float* rec = reinterpret_cast<const float*>(t.leaves + leaf);
+        float cx = rec[j], cy = rec[LEAF + j], cz = rec[2 * LEAF + j];
         const u32 posj = leaf * LEAF + j;
         const u32 r = __builtin_amdgcn_mbcnt_hi(static_cast<u32>(who >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<u32>(who), 0u));
         const bool mine = __builtin_amdgcn_inverse_ballot_w64(who);
@@ -935,10 +853,9 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
         __builtin_amdgcn_wave_barrier();  // (one wave: its LDS operations complete in order; this only pins the compiler's order)
         // A step takes its keys with the lanes that have none switched off (v_cmpx, like the lane-per-query leaves) instead of a branch
         // round them: five scalar-pipe instructions less per step, and nearly every step has a lane that takes one.  A row address
-        // beyond the column (PCPX_PACKED_FREE > 0) becomes the spare word's by bit arithmetic: a compare and select through VCC costs a
+        // beyond the column (packed_free > 0) becomes the spare word's by bit arithmetic: a compare and select through VCC costs a
         // register for the spare address and two wait states.
         const u64 saved = save_exec();
-        const u32 per_step = PCPX_PACKED_NODE > 0 ? 64u >> sh : 8u;
         u32 s = 0;  // (how_many >= 1: some lane needs the leaf)
         do {
             const float4 q = pub_q[s + i];
@@ -973,7 +890,7 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
                              : [at] "=&v"(at)
                              : [d2] "v"(d2), [tau] "v"(q.w), [slot] "v"(slot), [pos] "v"(posj), [saved] "s"(saved)
                              : "vcc", "memory");
-            s += per_step;
+            s += 8u;
         } while (s < how_many);
         __builtin_amdgcn_wave_barrier();
         u32 now = wa;
@@ -982,7 +899,7 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
             reinterpret_cast<float*>(pub_q + r)[3] = -1.f;
         }
         __builtin_amdgcn_wave_barrier();
-        if (PCPX_PRIO_PACKED != PCPX_PRIO_BASE) __builtin_amdgcn_s_setprio(PCPX_PRIO_BASE);
+        __builtin_amdgcn_s_setprio(PRIO_BASE);
         if (packed_free == 0) {
             wa = now;
             return 0ull;
@@ -1001,9 +918,7 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
         }
     };
     const u32 seed_count = s1 - s0;
-    u32 packed_limit = packed_leaves ? PCPX_PACKED_LEAVES : 0;
-    constexpr bool packed_nodes = packed_leaves && PCPX_PACKED_NODE > 0 && KCAP <= PCPX_PACKED_NODE_KCAP;
-    static_assert(!packed_nodes || (UNIT_LEAVES == 1 && PCPX_PACKED_NODE <= PCPX_PACKED_LEAVES), "the node form: one leaf per unit, one publish slot per needing lane");
+    u32 packed_limit = packed_leaves ? PACKED_LEAVES : 0;
     for (u32 rounds = 0;;) {  // (rounds != 0: a shell round -- asked of the counter, a bool carried round the loop becomes a lane mask)
         // (wave-uniform as it is, but carried round a loop whose exit hipcc takes for lane-dependent -- `cap` comes out of lane exchanges --
         //  it counts as a vector value, and a scalar flag made from it is an "illegal VGPR to SGPR copy")
@@ -1016,11 +931,9 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
         // at, as leaves direct_first + c.  A leaf inside the seed range was seen under a larger tau than any later one: skipped.
         if (STATS) tc_mark = __builtin_amdgcn_s_memtime();
         u32 direct = 0, direct_first = 0;
-        u32 sh = 3u;  // (packed_nodes: 5 while `direct` stands for a last-level node as a whole)
         for (;;) {
             if (direct == 0) {
                 if (wk.done()) break;
-                if (PCPX_PRIO_WALK != PCPX_PRIO_BASE) __builtin_amdgcn_s_setprio(PCPX_PRIO_WALK);
                 u32 node;
                 const int h = wk.pop(node);
                 ++st_expand;
@@ -1028,32 +941,10 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
                     wk.expand(t, h, node, need);
                 } else {
                     direct_first = node << LOGW;
-                    if (packed_nodes) {
-                        // (the node's own box -- a child box of its parent's record -- says how many lanes need it NOW; none: tau has shrunk since the parent was expanded)
-                        sh = 3u;
-                        u32 lanes_now = ~0u;
-                        u64 lanes = 0;
-                        if (packed_limit_now != 0) {
-                            const NodeBox own = load_const(t.nodes + (wk.level_base(t.depth - 1) + node));
-                            lanes = __builtin_amdgcn_ballot_w64(need(own));
-                            asm("s_bcnt1_i32_b64 %0, %1" : "=s"(lanes_now) : "s"(lanes) : "scc");  // (as __builtin_popcountll hipcc counts on the vector side)
-                        }
-                        if (lanes_now <= static_cast<u32>(PCPX_PACKED_NODE)) {
-                            wk.leaf_need[0] = lanes;
-                            wk.l = 0;
-                            wk.ploc = node;
-                            direct = __builtin_amdgcn_readfirstlane(lanes_now < 1u ? lanes_now : 1u);  // (wave-uniform as it is; hipcc 7.2 forms it on the vector side and then fails to bring it back: "illegal VGPR to SGPR copy")
-                            sh = 5u;
-                        } else {
-                            direct = wk.leaves_of(t, node, need);
-                        }
-                    } else {
-                        direct = wk.leaves_of(t, node, need);
-                    }
+                    direct = wk.leaves_of(t, node, need);
                 }
                 // (h = 0 is never popped: the build gives no tree a depth of 1 -- depth_of, pcpx_build.hip -- so leaves are only ever met under a
                 //  last-level node.  The case for it cost EVERY pop of the walk nine scalar instructions of dispatch.)
-                if (PCPX_PRIO_WALK != PCPX_PRIO_BASE) __builtin_amdgcn_s_setprio(PCPX_PRIO_BASE);
             }
             while (direct != 0) {
                 u32 loc;
@@ -1062,31 +953,22 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
                     asm("s_ff1_i32_b32 %0, %1\n\ts_bitset0_b32 %1, %0" : "=&s"(child), "+s"(direct));
                     loc = direct_first + child;
                 }
-                // (`loc` is a UNIT of the tree's bottom level: UNIT_LEAVES consecutive leaf records under one box, looked at one after the
-                //  other for the lanes that need the unit; the seed range is whole units)
-                if ((packed_nodes && sh == 5u) || loc * UNIT_LEAVES - s0 >= seed_count) {
+                if (loc - s0 >= seed_count) {
                     if (STATS) tc_walk += __builtin_amdgcn_s_memtime() - tc_mark;
                     if (!packed_leaves) {
-#pragma unroll 1
-                        for (u32 leaf = loc * UNIT_LEAVES;; ++leaf) {  // (a needed unit's first leaf exists; UNIT_LEAVES = 1: no loop)
-                            fold_if_needed(true, false);
-                            candidates(leaf, rounds != 0u);
-                            if (UNIT_LEAVES == 1 || leaf + 1u == (loc + 1u) * UNIT_LEAVES || leaf + 1u >= t.nleaves) break;
-                        }
+                        fold_if_needed(true, false);
+                        candidates(loc, rounds != 0u);
                     } else {
                         const u32 c = loc & (W - 1u);
                         u64 who;
-                        u32 how_many_unit;
+                        u32 how_many;
                         asm("s_cmp_eq_u32 %[c], 2\n\ts_cselect_b64 %[w], %[n2], %[n3]\n\t"
                             "s_cmp_eq_u32 %[c], 1\n\ts_cselect_b64 %[w], %[n1], %[w]\n\t"
                             "s_cmp_eq_u32 %[c], 0\n\ts_cselect_b64 %[w], %[n0], %[w]\n\t"
                             "s_bcnt1_i32_b64 %[m], %[w]"
-                            : [w] "=&s"(who), [m] "=s"(how_many_unit)
+                            : [w] "=&s"(who), [m] "=s"(how_many)
                             : [c] "s"(c), [n0] "s"(wk.leaf_need[0]), [n1] "s"(wk.leaf_need[1]), [n2] "s"(wk.leaf_need[2]), [n3] "s"(wk.leaf_need[3])
                             : "scc");
-#pragma unroll 1
-                        for (u32 leaf = loc * UNIT_LEAVES;; ++leaf) {  // (a needed unit's first leaf exists; UNIT_LEAVES = 1: no loop)
-                        u32 how_many = how_many_unit;
                         // Only a lane that needs the leaf can take keys from it (its box distance was within a tau that has only
                         // shrunk since, and no point of the leaf is nearer than its box): fold if one of THOSE could not take LEAF more.
                         // (The form is a NUMBER in a scalar register and "once more, after a fold" a threshold of 0: as two bools carried round
@@ -1101,23 +983,16 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
                             if ((__builtin_amdgcn_ballot_w64(wa >= full_from) & todo) != 0) fold(false);
                             if (packed_form == 0u) break;
                             if (STATS) tc_mark = __builtin_amdgcn_s_memtime();
-                            todo = packed_leaf(leaf, todo, how_many, sh);
-                            if (COST) st_steps += (how_many + (64u >> sh) - 1u) >> (6u - sh);
+                            todo = packed_leaf(loc, todo, how_many);
+                            if (COST) st_steps += (how_many + 7u) >> 3;
                             if (STATS) {
                                 asm volatile("" ::"v"(wa));
                                 tc_leaf += __builtin_amdgcn_s_memtime() - tc_mark;
                             }
-                            if (__builtin_expect(todo == 0, 1)) break;  // (else, PCPX_PACKED_FREE > 0 only and rare: columns ran full -- fold, and once more for their lanes)
+                            if (__builtin_expect(todo == 0, 1)) break;  // (else, packed_free > 0 only and rare: columns ran full -- fold, and once more for their lanes)
                             packed_take_back(todo);
                             how_many = static_cast<u32>(__builtin_popcountll(todo));
                             full_from = 0u;  // (every lane of `todo` has a full column, whatever its address was taken back to: fold)
-                            if (packed_nodes && sh == 5u) {  // (a node: its 32 points may be more than a column holds -- leaf by leaf for those lanes)
-                                sh = 3u;
-                                direct = (1u << W) - 1u;
-#pragma unroll
-                                for (int cc = 0; cc < W; ++cc) wk.leaf_need[cc] = todo;
-                                break;
-                            }
                         }
                         if (packed_form != 0u) {
                             if (COST) ++st_sparse;
@@ -1126,10 +1001,8 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
                             //  `appended` figure was that difference and came out as 1.7e14)
                             if (STATS) ++st_leaves, ++st_sparse, st_owners += how_many;
                         } else {
-                            candidates(leaf, rounds != 0u);
+                            candidates(loc, rounds != 0u);
                         }
-                        if (UNIT_LEAVES == 1 || leaf + 1u == (loc + 1u) * UNIT_LEAVES || leaf + 1u >= t.nleaves) break;
-                        }  // the unit's next leaf
                     }
                     if (STATS) tc_mark = __builtin_amdgcn_s_memtime();
                 }
@@ -1156,7 +1029,7 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
         // next radius^2; the last round is uncapped: when the cap covers the whole cloud from any query inside 2x its box, when
         // it cannot grow (a cap of 0: more than half of the sampled lanes sit on >= k coincident points and eps is 0), or
         // after 12 rounds
-        const float grown = cap * PCPX_CAP_GROW;
+        const float grown = cap * CAP_GROW;
         ++rounds;
         packed_limit = 0;  // (the later rounds want lo_d2 < d2 as well: lane-per-query leaves.  Measured, round 5: the packed form there with a shell
                            //  test, and a raised priority for a group from its second round on -- neither moved the longest groups nor the rate:
@@ -1218,7 +1091,6 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
         }
     }
     const int first_slot = KCAP - static_cast<int>(k);
-    if (PCPX_PRIO_EPI != PCPX_PRIO_BASE) __builtin_amdgcn_s_setprio(PCPX_PRIO_EPI);
     // (the cold arguments are read again where the epilogue needs them: nothing read through `ka` above is alive any more)
     if (MULTI) {  // raw (d2, sorted position) keys of this pass; rows are built by k_assemble
         const MultiPass mp = cold(&knn_args_here()->mp);
@@ -1278,11 +1150,9 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
     }
     // (the column goes back to the chunked compaction's invariant -- empty slots hold PAD_KEY -- at the end of this function)
     auto restore_column = [&]() {
-        if (PCPX_COMPACT_BY8 && (KCAP <= 16 || PCPX_BY8_K32)) {
-            const u64 pad = pad_key_here();
+        const u64 pad = pad_key_here();  // (single-pass kernels only: a multi-pass kernel has returned above)
 #pragma unroll
-            for (int r = 0; r < (KCAP + 1) / 2; ++r) col[r * 64] = pad;
-        }
+        for (int r = 0; r < (KCAP + 1) / 2; ++r) col[r * 64] = pad;
     };
 
     if (!valid) {
@@ -1433,8 +1303,8 @@ constexpr u32 QUEUE_STRIDE = 16;  // u32 per queue counter (64 B)
 constexpr u32 ORDER_HEADER = 16, ORDER_PARTS = 8, ORDER_PART_SHIFT = 28, ORDER_GROUP_MASK = (1u << ORDER_PART_SHIFT) - 1u;
 inline u64 order_entries(u64 ngroups) { return ORDER_HEADER + ORDER_PARTS * 8ull * ((ngroups + 7) / 8); }
 
-template <int KCAP, bool SELF, int DIAG, bool MULTI = false, bool EPS_EACH = !PCPX_DEFER_EPS, int NZ = 0>
-__global__ __launch_bounds__(64 * knn_wpb(KCAP, MULTI), KCAP <= 8 ? PCPX_MINW8 : KCAP <= 16 ? PCPX_MINW : PCPX_MINW32) void k_knn(
+template <int KCAP, bool SELF, int DIAG, bool MULTI = false, bool EPS_EACH = false, int NZ = 0>
+__global__ __launch_bounds__(64 * knn_wpb(KCAP, MULTI), KCAP <= 8 ? MINW8 : KCAP <= 16 ? MINW16 : MINW32) void k_knn(
     const KnnArgs a)
 {
     constexpr bool STATS = DIAG == 1;
@@ -1449,9 +1319,9 @@ __global__ __launch_bounds__(64 * knn_wpb(KCAP, MULTI), KCAP <= 8 ? PCPX_MINW8 :
     u64* const rows = lds + static_cast<size_t>(wib) * lds_rows(BUF, MULTI, MULTI ? 0 : KCAP) * 64;  // this wave's rows
     u64* col = rows + lane;
     float* pub = reinterpret_cast<float*>(rows + BUF * 64);  // packed_leaf's rows (pack_rows), behind the buffer's
-    if (pack_rows(MULTI, KCAP) > 0 && lane < static_cast<u32>(PCPX_PACKED_LEAVES)) pub[4u * lane + 3u] = -1.f;  // its invariant: a slot that holds no query holds tau = -1
+    if (pack_rows(MULTI, KCAP) > 0 && lane < static_cast<u32>(PACKED_LEAVES)) pub[4u * lane + 3u] = -1.f;  // its invariant: a slot that holds no query holds tau = -1
     if (blockIdx.x == 0 && wib == 0 && lane < 8u) a.queue_clear[lane * QUEUE_STRIDE] = 0u;  // (the next launch's counters: prepare_queue)
-    if (PCPX_COMPACT_BY8 && !MULTI && (KCAP <= 16 || PCPX_BY8_K32)) {  // the chunked compaction's invariant: empty slots hold PAD_KEY
+    if (chunked_compaction(MULTI)) {  // the chunked compaction's invariant: empty slots hold PAD_KEY
         const u64 pad = pad_key_here();
 #pragma unroll
         for (int j = 0; j < BUF; ++j) col[j * 64] = pad;
@@ -1554,7 +1424,7 @@ int prepare_queue(Index& ix)
 // performance decision, both forms give the same rows).  Index::eps_test_mode (pcpx_debug_eps_test_mode) forces either.
 static float eps_box_threshold(const Index& ix, float eps)
 {
-    if (!PCPX_DEFER_EPS || ix.eps_test_mode == 2) return -1.f;
+    if (ix.eps_test_mode == 2) return -1.f;
     if (!(eps > 0.f)) return 0.f;  // nothing is inside an empty box
     const double t = 3.0 * static_cast<double>(eps) * static_cast<double>(eps) * (1.0 + 1e-6);
     if (!(t < 1e37)) return ix.eps_test_mode == 1 ? std::numeric_limits<float>::infinity() : -1.f;
@@ -1587,27 +1457,10 @@ static float eps_box_threshold(const Index& ix, float eps)
 // epilogues (a fifth of a mean group each, for less than 1 % of the groups).
 // One block per queue.
 constexpr u32 LPT_MIN_GROUPS = 512;
-#ifndef PCPX_LPT_SPLIT
-#define PCPX_LPT_SPLIT 1  // class-0 groups are handed out as ORDER_PARTS entries of 8 lanes each
-#endif
-#ifndef PCPX_TAIL_SPLIT
-#define PCPX_TAIL_SPLIT 0  // 1: the groups of a launch's last round in pieces when that round is at most half full.  Measured (round 5,
-                           // tools/ab_sizes.py): SLOWER -- 1 M queries 2 130 -> 1 880 Mq/s, 0.5 M 1 520 -> 1 380, 2 M 2 475 -> 2 370: a piece of 16
-                           // lanes costs most of a group (its seed leaves, its walk's common part, its epilogue), not half of one
-#endif
-#ifndef PCPX_LPT_HI_PCT
-#define PCPX_LPT_HI_PCT 200ull   // class 0: groups that took more than twice their queue's mean ...
-#endif
-#ifndef PCPX_LPT_MID_PCT
-#define PCPX_LPT_MID_PCT 150ull  // ... class 1: more than 1.5 x.  (7/4 and 9/8 -- a third of a uniform cloud's groups out of curve order -- cost the
-                                 //  10 M uniform launch 4 %: the queue's walk along the curve is what keeps its XCD's L2 warm.)
-#endif
-// tail_parts (0, 2, 4, 8) / tail_groups: the last tail_groups groups of every queue's list are handed out in tail_parts pieces each
-// -- the launch's last round, when it is at most 1 / tail_parts full: a persistent launch of G groups on W resident waves ends with
-// G mod W groups on as many waves while the others idle for a whole group's time (1 M queries: 2.2 rounds); in pieces they fill
-// the round, and a piece of 16 lanes takes about half a group's time.  gtime == nullptr: no recorded times, curve order.
-__global__ __launch_bounds__(1024) void k_make_order(const u32* __restrict__ gtime, u32 ngroups, u32 group_first, u32* __restrict__ order, u32 tail_parts,
-                                                     u32 tail_groups)
+constexpr unsigned long long LPT_HI_PCT = 200;   // class 0: groups that took more than twice their queue's mean ...
+constexpr unsigned long long LPT_MID_PCT = 150;  // ... class 1: more than 1.5 x.  (7/4 and 9/8 -- a third of a uniform cloud's groups out of curve order -- cost the
+                                                 //  10 M uniform launch 4 %: the queue's walk along the curve is what keeps its XCD's L2 warm.)
+__global__ __launch_bounds__(1024) void k_make_order(const u32* __restrict__ gtime, u32 ngroups, u32 group_first, u32* __restrict__ order)
 {
     __shared__ unsigned long long sum_s;
     __shared__ u32 cnt_s[3], base_s[3], wave_s[3][16];
@@ -1622,16 +1475,14 @@ __global__ __launch_bounds__(1024) void k_make_order(const u32* __restrict__ gti
     if (t < 3) cnt_s[t] = 0;
     __syncthreads();
     unsigned long long mine = 0;
-    if (gtime)
-        for (u32 i = qbeg + t; i < qend; i += 1024u) mine += gtime[i];
+    for (u32 i = qbeg + t; i < qend; i += 1024u) mine += gtime[i];
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
     if (lane == 0) atomicAdd(&sum_s, mine);
     __syncthreads();
     const unsigned long long mean = sum_s / (qend - qbeg);
-    const unsigned long long hi = mean * PCPX_LPT_HI_PCT / 100ull, mid = mean * PCPX_LPT_MID_PCT / 100ull;
+    const unsigned long long hi = mean * LPT_HI_PCT / 100ull, mid = mean * LPT_MID_PCT / 100ull;
     auto cls = [&](u32 i) -> u32 {
-        if (!gtime) return 2u;
         const u32 v = gtime[i];
         return v > hi ? 0u : v > mid ? 1u : 2u;
     };
@@ -1645,14 +1496,11 @@ __global__ __launch_bounds__(1024) void k_make_order(const u32* __restrict__ gti
         if (lane == 0 && v) atomicAdd(&cnt_s[b], v);
     }
     __syncthreads();
-    const u32 whole2 = cnt_s[2] > tail_groups ? cnt_s[2] - tail_groups : 0u;  // class-2 groups handed out whole; the rest in tail_parts pieces
-    const u32 tail_n = tail_parts ? cnt_s[2] - whole2 : 0u;
-    __syncthreads();
     if (t == 0) {
         base_s[0] = 0;
         base_s[1] = cnt_s[0];
         base_s[2] = cnt_s[0] + cnt_s[1];
-        order[blockIdx.x] = (PCPX_LPT_SPLIT ? ORDER_PARTS : 1u) * cnt_s[0] + cnt_s[1] + (cnt_s[2] - tail_n) + tail_parts * tail_n;
+        order[blockIdx.x] = ORDER_PARTS * cnt_s[0] + cnt_s[1] + cnt_s[2];
     }
     __syncthreads();
     for (u32 i0 = qbeg; i0 < qend; i0 += 1024u) {
@@ -1671,19 +1519,11 @@ __global__ __launch_bounds__(1024) void k_make_order(const u32* __restrict__ gti
             u32 before = 0;
             for (u32 ww = 0; ww < w; ++ww) before += wave_s[b][ww];
             const u32 at = ORDER_HEADER + ORDER_PARTS * qbeg;
-            if (b == 0 && PCPX_LPT_SPLIT) {
+            if (b == 0) {
 #pragma unroll
                 for (u32 part = 0; part < ORDER_PARTS; ++part) order[at + ORDER_PARTS * (base_s[0] + before + below) + part] = (group_first + i) | ((part + 1u) << ORDER_PART_SHIFT);
             } else {
-                const u32 slot = (PCPX_LPT_SPLIT ? ORDER_PARTS - 1u : 0u) * cnt_s[0] + base_s[b] + before + below;  // (were every class-1 / -2 group whole)
-                const u32 i2 = base_s[b] + before + below - (cnt_s[0] + cnt_s[1]);                                 // class 2: its number in the class
-                if (b == 2 && tail_n != 0u && i2 >= cnt_s[2] - tail_n) {
-                    const u32 first_piece = slot - (i2 - (cnt_s[2] - tail_n)) + tail_parts * (i2 - (cnt_s[2] - tail_n));
-                    const u32 code0 = tail_parts == 8u ? 1u : tail_parts == 4u ? 9u : 13u;
-                    for (u32 part = 0; part < tail_parts; ++part) order[at + first_piece + part] = (group_first + i) | ((code0 + part) << ORDER_PART_SHIFT);
-                } else {
-                    order[at + slot] = group_first + i;
-                }
+                order[at + (ORDER_PARTS - 1u) * cnt_s[0] + base_s[b] + before + below] = group_first + i;  // (behind the class-0 groups' pieces)
             }
         }
         __syncthreads();
@@ -1738,26 +1578,16 @@ static int launch_knn_form(Index& ix, const QueryView& qv, u64 gfirst, u64 gcoun
     const u32 pgrid = persistent_grid(ix, reinterpret_cast<const void*>(fn), 64 * WPB, lds, gcount, WPB);
     if (SELF && ix.tuning.lpt && gcount >= LPT_MIN_GROUPS) {
         Index::Sched& sc = ix.sched;
-        // the launch's last round: G mod W groups, in 2 / 4 / 8 pieces each if that still fits the resident waves (k_make_order)
-        const u64 waves = static_cast<u64>(pgrid) * WPB, rest = gcount % waves;
-        u32 tail_parts = 0;
-        if (PCPX_TAIL_SPLIT && gcount > waves && rest != 0) tail_parts = 8 * rest <= waves ? 8u : 4 * rest <= waves ? 4u : 2 * rest <= waves ? 2u : 0u;
-        const u32 tail_groups = tail_parts ? static_cast<u32>((rest + 7) / 8) : 0u;  // (per queue)
         const bool same = sc.state != 0 && sc.gf == gfirst && sc.gc == gcount && sc.kcap == KCAP && sc.k == k;
-        if (same && (sc.state == 1 || sc.state == 3)) {  // times recorded: the order by them (and the tail in pieces)
-            k_make_order<<<8, 1024, 0, ix.stream>>>(sc.d_gtime, static_cast<u32>(gcount), gf, sc.d_order, tail_parts, tail_groups);
+        if (same && sc.state == 1) {  // times recorded: the order by them
+            k_make_order<<<8, 1024, 0, ix.stream>>>(sc.d_gtime, static_cast<u32>(gcount), gf, sc.d_order);
             sc.state = 2;
         }
         if (same && sc.state == 2) {
             sch.order = sc.d_order;
-        } else if (sched_reserve(ix, gcount) == PCPX_OK) {  // a new question: record; curve order, the tail in pieces if it pays
+        } else if (sched_reserve(ix, gcount) == PCPX_OK) {  // a new question: record; curve order
             sch.gtime = sc.d_gtime;
             sc.gf = gfirst, sc.gc = gcount, sc.kcap = KCAP, sc.k = k, sc.state = 1;
-            if (tail_parts) {
-                k_make_order<<<8, 1024, 0, ix.stream>>>(nullptr, static_cast<u32>(gcount), gf, sc.d_order, tail_parts, tail_groups);
-                sch.order = sc.d_order;
-                sc.state = 3;  // (recorded with an order in use: a group handed out in pieces leaves one piece's time, which is what it is worth)
-            }
         }
     }
     ProfileScope prof(ix, PCPX_K_KNN);
@@ -1798,7 +1628,7 @@ template <int KCAP>
 static int launch_knn_t(Index& ix, const QueryView& qv, bool self, u64 gfirst, u64 gcount, u32 k, float eps, const KnnOutputs& o)
 {
     const float thr = eps_box_threshold(ix, eps);
-    if (PCPX_DEFER_EPS && thr >= 0.f) {
+    if (thr >= 0.f) {
         if (k < static_cast<u32>(KCAP)) {  // at least one sentinel slot: its compare-exchanges are compiled out
             return self ? launch_knn_form<KCAP, true, false, 1>(ix, qv, gfirst, gcount, k, eps, thr, o)
                         : launch_knn_form<KCAP, false, false, 1>(ix, qv, gfirst, gcount, k, eps, thr, o);

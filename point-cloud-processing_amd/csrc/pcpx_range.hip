@@ -319,16 +319,15 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void k_range_aabb(TreeView t,
     // the walk of walk_needed_leaves (pcpx_device.h) with a last-level node's needed children in a scalar loop
     WalkerT<true, true> wk;
     u32 nexp = 0;
-    if (wk.start(t, need, nexp))
-        for (u32 leaf = 0; leaf < static_cast<u32>(UNIT_LEAVES) && leaf < t.nleaves; ++leaf) leaf_points(leaf);
-    while (!wk.done()) {  // one pop per trip: a node is expanded; a last-level node looks at its needed units itself
+    if (wk.start(t, need, nexp) && t.nleaves != 0u) leaf_points(0u);
+    while (!wk.done()) {  // one pop per trip: a node is expanded; a last-level node looks at its needed leaves itself
         u32 loc;
         const int h = wk.pop(loc);
         if (h > 1) {
             wk.expand(t, h, loc, need);
         } else {  // (no leaf is ever popped)
             u32 needed = wk.leaves_of(t, loc, need);
-            // (one copy of the leaf forms, the needed children in a loop: written out four times two records they cost the count kernel
+            // (one copy of the leaf forms, the needed children in a loop: written out four times they cost the count kernel
             //  133 saved scalar registers)
 #pragma nounroll
             while (needed != 0u) {
@@ -343,9 +342,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void k_range_aabb(TreeView t,
                     : [w] "=&s"(who), [m] "=s"(how_many)
                     : [c] "s"(c), [n0] "s"(wk.leaf_need[0]), [n1] "s"(wk.leaf_need[1]), [n2] "s"(wk.leaf_need[2]), [n3] "s"(wk.leaf_need[3])
                     : "scc");
-                const u32 first = ((loc << LOGW) + c) * UNIT_LEAVES;
-#pragma unroll 1
-                for (u32 leaf = first; leaf < first + UNIT_LEAVES && leaf < t.nleaves; ++leaf) {
+                const u32 leaf = (loc << LOGW) + c;
+                if (leaf < t.nleaves) {
                     if (how_many <= PACKED_LEAVES) packed_leaf(t.leaves + leaf, who, how_many);
                     else leaf_points(leaf);
                 }
@@ -381,7 +379,7 @@ __global__ __launch_bounds__(64) void k_range_one(TreeView t, float a0, float a1
     };
     auto level_base = [](int d) { return d == 0 ? 0u : (0x55555555u >> (32 - 2 * d)); };
     // real nodes of tree level l (the ones the build writes: the children of a real node need not be real)
-    auto nreal = [&](int l) { return (t.nunits() + (1u << (2 * (t.depth - l))) - 1u) >> (2 * (t.depth - l)); };
+    auto nreal = [&](int l) { return (t.nleaves + (1u << (2 * (t.depth - l))) - 1u) >> (2 * (t.depth - l)); };
     u32 cnt = 0, m = 0;
     bool overflow = false;
     int cur = 0;
@@ -420,13 +418,13 @@ __global__ __launch_bounds__(64) void k_range_one(TreeView t, float a0, float a1
             cur ^= 1;
             __syncthreads();
         }
-        // the points of the surviving units, one per lane, in leaf (= curve) order
-        for (u32 c0 = 0; c0 < static_cast<u32>(UNIT_POINTS) * m && !overflow; c0 += 64u) {
+        // the points of the surviving leaves, one per lane, in leaf (= curve) order
+        for (u32 c0 = 0; c0 < static_cast<u32>(LEAF) * m && !overflow; c0 += 64u) {
             const u32 c = c0 + lane;
             bool in = false;
             u32 id = 0;
-            if (c < static_cast<u32>(UNIT_POINTS) * m) {
-                const u32 leaf = front[cur][c / UNIT_POINTS] * UNIT_LEAVES + (c % UNIT_POINTS) / LEAF;
+            if (c < static_cast<u32>(LEAF) * m) {
+                const u32 leaf = front[cur][c / LEAF];
                 if (leaf < t.nleaves) {
                     const Leaf& lf = t.leaves[leaf];
                     const u32 sl = c & 7u;

@@ -680,10 +680,7 @@ int sort_keys_u64(void* tmp, size_t& tmp_bytes, const u64* kin, u64* kout, u64 n
         (void)hipGetLastError();
         if (dev >= 0 && dev < 64) cus_of_device[dev] = cus;
     }
-#ifndef PCPX_SORT_PERSISTENT
-#define PCPX_SORT_PERSISTENT 1  // 0: one block per tile (the dispatcher hands out blocks; every block still takes its tile by ticket)
-#endif
-    const u64 resident = PCPX_SORT_PERSISTENT ? static_cast<u64>(cus) * (SORT_ITEMS <= 8 ? 6 : SORT_ITEMS <= 16 ? 4 : 3) : ~0ull;
+    const u64 resident = static_cast<u64>(cus) * (SORT_ITEMS <= 8 ? 6 : SORT_ITEMS <= 16 ? 4 : 3);
     const u32 grid_top = static_cast<u32>(ntiles);  // (one tile per block: no chain, nothing to keep resident)
     const u32 grid_seg = static_cast<u32>(L.ntiles_max < resident ? L.ntiles_max : resident);
     // ping-pong between tmp and out so that the LAST pass writes out
