@@ -215,6 +215,14 @@ CLUSTER_SIGNATURES = {
     "pcpx_cluster_self": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, u64p]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/pcpx_subsample.h (Poisson-disk subsampling)
+PCPX_SUBSAMPLE_NONE = 0xFFFFFFFF
+PCPX_SUBSAMPLE_ROUND_BATCH = 4
+SUBSAMPLE_SIGNATURES = {
+    "pcpx_subsample_self_dev": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u32p]),
+    "pcpx_subsample_self": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, u64p, u32p]),
+}
+
 
 def load():
     """Load libpcpx.so; raises if it has not been built (run __graft_entry__.build())."""
@@ -227,7 +235,8 @@ def load():
             "There is no CPU fallback for the pcpx compute path." % LIB_PATH)
     _share_hip_runtime_with_torch()
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(RADIUS_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(RADIUS_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items())\
+            + list(SUBSAMPLE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -286,6 +286,39 @@ class Index:
                                               C.c_void_p(d_labels) if d_labels else None,
                                               *(C.c_void_p(d) if d else None for d in (d_core, d_counts, d_cluster_count))))
 
+    # ---- Poisson-disk subsampling (include/pcpx_subsample.h) ----
+    def subsample(self, radius, seed=0, want_keep=False, want_owner=False, want_rounds=False):
+        """The subsample in which no two points are within `radius` of each other and every dropped indexed point has a kept point
+        within `radius`: the kept set of the greedy loop that visits the points in ascending fmix32(input index ^ seed) and keeps a
+        point iff no kept point is in its sphere (the rule of range_count_self).  A point outside the voxel grid is dropped;
+        radius 0 keeps one point of every set of exact duplicates.  Returns the kept input indices, ascending (uint32)[, the keep
+        mask bool (n_in,)][, owners uint32 (n_in,): the kept point in the row's sphere of smallest (d2, index), the row itself if it
+        is kept, 0xFFFFFFFF outside the grid][, the round launches issued]."""
+        keep = np.empty(self.n_in, np.uint8)
+        owner = np.empty(self.n_in, np.uint32) if want_owner else None
+        kept = np.empty(self.n_in, np.uint32)
+        count = C.c_uint64(0)
+        rounds = C.c_uint32(0)
+        check(self._lib.pcpx_subsample_self(self._h, float(radius), int(seed) & 0xFFFFFFFF, 0, _vp(keep), _vp(owner), _vp(kept), C.byref(count),
+                                            C.byref(rounds)))
+        out = (kept[:int(count.value)].copy(),)
+        if want_keep:
+            out += (keep.astype(bool),)
+        if want_owner:
+            out += (owner,)
+        if want_rounds:
+            out += (int(rounds.value),)
+        return out[0] if len(out) == 1 else out
+
+    def subsample_dev(self, radius, d_keep, seed=0, d_owner=None, d_kept_rows=None, d_kept_count=None):
+        """Device form (pointers to device arrays: keep uint8 and owner uint32 by input row, kept_rows uint32 with room for n_in
+        entries, d_kept_count one uint64).  Synchronises the index's stream between rounds; what follows the last round is only
+        enqueued.  Returns the round launches issued."""
+        rounds = C.c_uint32(0)
+        check(self._lib.pcpx_subsample_self_dev(self._h, float(radius), int(seed) & 0xFFFFFFFF, 0, C.c_void_p(d_keep) if d_keep else None,
+                                                *(C.c_void_p(d) if d else None for d in (d_owner, d_kept_rows, d_kept_count)), C.byref(rounds)))
+        return int(rounds.value)
+
     # ---- normals ----
     def normals_knn_self(self, k, eps=1e-5, want_knn=False):
         nrm = np.empty((self.n_in, 3), np.float32)
