@@ -223,6 +223,17 @@ SUBSAMPLE_SIGNATURES = {
     "pcpx_subsample_self": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, u64p, u32p]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/pcpx_segment.h (smooth-surface segmentation)
+PCPX_SEGMENT_NOISE = 0xFFFFFFFF
+PCPX_SEGMENT_COMPACT = 1
+PCPX_SEGMENT_ORIENTED = 2
+SEGMENT_SIGNATURES = {
+    "pcpx_segment_self_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    "pcpx_segment_self": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p,
+                                    C.c_void_p, u64p]),
+}
+
 
 def load():
     """Load libpcpx.so; raises if it has not been built (run __graft_entry__.build())."""
@@ -236,7 +247,7 @@ def load():
     _share_hip_runtime_with_torch()
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(RADIUS_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items())\
-            + list(SUBSAMPLE_SIGNATURES.items()):
+            + list(SUBSAMPLE_SIGNATURES.items()) + list(SEGMENT_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

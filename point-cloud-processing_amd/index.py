@@ -286,6 +286,57 @@ class Index:
                                               C.c_void_p(d_labels) if d_labels else None,
                                               *(C.c_void_p(d) if d else None for d in (d_core, d_counts, d_cluster_count))))
 
+    # ---- smooth-surface segmentation (include/pcpx_segment.h) ----
+    @staticmethod
+    def _segment_threshold(max_angle, min_cos):
+        """min_cos as the C ABI takes it: given, or float32(cos(float64(max_angle))) of an angle in radians; exactly one of the two"""
+        if (max_angle is None) == (min_cos is None):
+            raise ValueError("give exactly one of max_angle and min_cos")
+        return float(np.float32(np.cos(np.float64(max_angle)))) if min_cos is None else float(min_cos)
+
+    @staticmethod
+    def _segment_flags(oriented, compact):
+        return (_capi.PCPX_SEGMENT_COMPACT if compact else 0) | (_capi.PCPX_SEGMENT_ORIENTED if oriented else 0)
+
+    def segment(self, normals, radius, max_angle=None, min_cos=None, curvature=None, max_curvature=float("inf"), min_size=1, oriented=False,
+                compact=True, want_smooth=False):
+        """Smooth surface patches of the indexed cloud (normal-constrained region growing in its order-independent form): two points
+        are joined iff one is in the other's sphere (the rule of range_count_self) and their normals agree, |n_i . n_j| >= min_cos
+        in float32 (oriented: n_i . n_j >= min_cos); `normals` (n_in x 3) are used as given.  Segments are the connected
+        components of the smooth points -- all indexed points, or with `curvature` (n_in) those with curvature <= max_curvature;
+        a non-smooth point joins the smallest-labelled compatible smooth point in its sphere; segments of fewer than min_size rows,
+        unreached points and points outside the voxel grid are noise: label 0xFFFFFFFF.  max_angle (radians) is converted as
+        float32(cos(float64(max_angle))).  compact: labels 0 ... S-1 ordered by representative, else the representative itself
+        (the segment's smallest smooth input index).
+        Returns (labels uint32 (n_in,), number of segments[, smooth bool (n_in,)])."""
+        threshold = self._segment_threshold(max_angle, min_cos)
+        nrm = _f32(normals, 3)
+        if len(nrm) != self.n_in:
+            raise ValueError("one normal per input point")
+        curv = None
+        if curvature is not None:
+            curv = _f32(curvature).reshape(-1)
+            if len(curv) != self.n_in:
+                raise ValueError("one curvature per input point")
+        labels = np.empty(self.n_in, np.uint32)
+        smooth = np.empty(self.n_in, np.uint8) if want_smooth else None
+        nsegments = C.c_uint64(0)
+        check(self._lib.pcpx_segment_self(self._h, _vp(nrm), _vp(curv), float(radius), threshold, float(max_curvature), int(min_size),
+                                          self._segment_flags(oriented, compact), _vp(labels), _vp(smooth), C.byref(nsegments)))
+        out = (labels, int(nsegments.value))
+        if want_smooth:
+            out += (smooth.astype(bool),)
+        return out
+
+    def segment_dev(self, d_normals, radius, d_labels, max_angle=None, min_cos=None, d_curvature=None, max_curvature=float("inf"), min_size=1,
+                    oriented=False, compact=True, d_smooth=None, d_segment_count=None):
+        """Device form (pointers to device arrays by input row: normals float32 x 3, curvature float32, labels uint32, smooth uint8;
+        d_segment_count one uint64), enqueued on the index's stream."""
+        check(self._lib.pcpx_segment_self_dev(self._h, *(C.c_void_p(d) if d else None for d in (d_normals, d_curvature)), float(radius),
+                                              self._segment_threshold(max_angle, min_cos), float(max_curvature), int(min_size),
+                                              self._segment_flags(oriented, compact),
+                                              *(C.c_void_p(d) if d else None for d in (d_labels, d_smooth, d_segment_count))))
+
     # ---- Poisson-disk subsampling (include/pcpx_subsample.h) ----
     def subsample(self, radius, seed=0, want_keep=False, want_owner=False, want_rounds=False):
         """The subsample in which no two points are within `radius` of each other and every dropped indexed point has a kept point
