@@ -1112,7 +1112,7 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
     u32* const pos_col = reinterpret_cast<u32*>(col);
     auto pos_slot = [&](int s) -> u32& { return pos_col[(s >> 1) * 128 + (s & 1)]; };
 #pragma unroll
-    for (int s = 0; s < KCAP; ++s) {
+    for (int s = NZ; s < KCAP; ++s) {  // (a slot below NZ holds the sentinel in every lane: no position, no id, never exchanged)
         u64 key = best[s];
         bool real = s >= first_slot && key != PAD_KEY;
         u32 ps = real ? static_cast<u32>(key) : 0u;
@@ -1200,7 +1200,7 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
     };
     if (whole_rows) store_whole_rows(std::integral_constant<int, NZ>{});
 #pragma unroll
-    for (int s = 0; s < KCAP; ++s) {
+    for (int s = NZ; s < KCAP; ++s) {  // (first_slot >= NZ)
         int j = s - first_slot;
         if (j >= 0) {
             u64 key = best[s];
@@ -1227,7 +1227,7 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
     if (o.meandist) {
         float sum = 0.f;
 #pragma unroll
-        for (int s = 0; s < KCAP; ++s) {
+        for (int s = NZ; s < KCAP; ++s) {
             bool ok = (okmask >> s) & 1u;
             float d = sqrtf(__uint_as_float(static_cast<u32>(best[s] >> 32)));
             sum += ok ? d : 0.f;
@@ -1238,16 +1238,29 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
     // ---- fused pcp::estimate_normal over the row (normal_estimation.hpp:41-77), coordinates gathered
     //      from the leaf records in row order ----
     if (o.normals || o.centroids || (SELF && o.nc4)) {
-        float sx = 0.f, sy = 0.f, sz = 0.f;
+        // Each neighbour's leaf record is read ONCE, x, y and z together (its two cache lines are hot together), in the row's final
+        // order -- after the tie repair, so a coordinate never has to follow an exchange.  The keys are dead by now (rows, tau,
+        // count and mean distance are written): the coordinates take their 2 KCAP registers and KCAP more, which every kernel has
+        // at its budget without scratch (the positions' LDS column would have taken z otherwise).  The
+        // centroid and the scatter matrix below read what the lane holds: the same operations on the same values in the same
+        // order as with a gather per sum.
+        // (slots below NZ hold the sentinel in every lane: not gathered, and what they added to each sum was + 0.f)
+        float nbx[KCAP], nby[KCAP], nbz[KCAP];
 #pragma unroll
-        for (int s = 0; s < KCAP; ++s) {
-            bool ok = (okmask >> s) & 1u;
+        for (int s = NZ; s < KCAP; ++s) {
             const u32 ps = pos_slot(s);
             const Leaf& lf = t.leaves[ps / LEAF];
-            float x = lf.x[ps % LEAF], y = lf.y[ps % LEAF], z = lf.z[ps % LEAF];
-            sx += ok ? x : 0.f;
-            sy += ok ? y : 0.f;
-            sz += ok ? z : 0.f;
+            nbx[s] = lf.x[ps % LEAF];
+            nby[s] = lf.y[ps % LEAF];
+            nbz[s] = lf.z[ps % LEAF];
+        }
+        float sx = 0.f, sy = 0.f, sz = 0.f;
+#pragma unroll
+        for (int s = NZ; s < KCAP; ++s) {
+            bool ok = (okmask >> s) & 1u;
+            sx += ok ? nbx[s] : 0.f;
+            sy += ok ? nby[s] : 0.f;
+            sz += ok ? nbz[s] : 0.f;
         }
         float fn = static_cast<float>(found);
         float mx = sx / fn, my = sy / fn, mz = sz / fn;
@@ -1262,11 +1275,9 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
         }
         float c00 = 0.f, c10 = 0.f, c11 = 0.f, c20 = 0.f, c21 = 0.f, c22 = 0.f;
 #pragma unroll
-        for (int s = 0; s < KCAP; ++s) {
+        for (int s = NZ; s < KCAP; ++s) {
             bool ok = (okmask >> s) & 1u;
-            const u32 ps = pos_slot(s);
-            const Leaf& lf = t.leaves[ps / LEAF];
-            float x = lf.x[ps % LEAF], y = lf.y[ps % LEAF], z = lf.z[ps % LEAF];
+            float x = nbx[s], y = nby[s], z = nbz[s];
             float vx = ok ? x - mx : 0.f, vy = ok ? y - my : 0.f, vz = ok ? z - mz : 0.f;
             c00 += vx * vx;
             c10 += vy * vx;
