@@ -6,6 +6,7 @@
 #define PCP_GPU_DEVICE_INDEX_HPP
 
 #include "pcpx.h"
+#include "pcpx_features.h"
 #include "pcpx_radius.h"
 
 #include <array>
@@ -402,6 +403,21 @@ class device_index_t
         if (n)
             check(pcpx_range_neighbourhoods_batch(h_, centers, nullptr, radius, n, normals, centroids, mean_dist, count),
                   "pcpx_range_neighbourhoods_batch");
+    }
+    // Local shape features (pcpx_features.h) of the same neighbourhoods, in one launch of the sphere walk's features form: the
+    // scatter matrix's eigenvalues (x 3, ascending), the surface variation, the PCA normal (x 3), the principal axis (x 3) and the
+    // count.  Any output pointer may be null (not all).  _self: host arrays of `rows` rows; _self_dev: device arrays by input
+    // row, enqueued on the index's stream (synchronize() waits for it).
+    void shape_features_self(float radius, std::uint64_t rows, float* evals, float* curvature, float* normals, float* axes,
+                             std::uint32_t* count) const
+    {
+        if (rows) check(pcpx_shape_features_self(h_, radius, evals, curvature, normals, axes, count), "pcpx_shape_features_self");
+    }
+    void shape_features_self_dev(float radius, float* d_evals, float* d_curvature, float* d_normals, float* d_axes,
+                                 std::uint32_t* d_count) const
+    {
+        check(pcpx_shape_features_self_dev(h_, radius, 0, UINT64_MAX, d_evals, d_curvature, d_normals, d_axes, d_count),
+              "pcpx_shape_features_self_dev");
     }
     // propagate_normal_orientations over the index's own kNN graph, all on the GPU; normals: rows x 3, in place
     std::uint64_t orient_normals_self(std::uint32_t k, float eps, std::vector<float>& normals) const

@@ -17,7 +17,7 @@ SOURCES = ["pcpx_query.hip", "pcpx_few.hip", "pcpx_range.hip", "pcpx_cluster.hip
 HEADERS = [os.path.join(CSRC, "pcpx_internal.h"), os.path.join(CSRC, "pcpx_device.h"), os.path.join(CSRC, "pcpx_eig3.h"), os.path.join(CSRC, "pcpx_curve.h"),
            os.path.join(CSRC, "pcpx_curve_table.h"), os.path.join(CSRC, "pcpx_scan.h"), os.path.join(CSRC, "pcpx_unionfind.h"), os.path.join(CSRC, "pcpx_labels.h"),
            os.path.join(INCLUDE, "pcpx.h"), os.path.join(INCLUDE, "pcpx_radius.h"), os.path.join(INCLUDE, "pcpx_cluster.h"),
-           os.path.join(INCLUDE, "pcpx_subsample.h"), os.path.join(INCLUDE, "pcpx_segment.h")]
+           os.path.join(INCLUDE, "pcpx_subsample.h"), os.path.join(INCLUDE, "pcpx_segment.h"), os.path.join(INCLUDE, "pcpx_features.h")]
 ARCH = "gfx950"
 # -ffp-contract=off: the reference evaluates dx*dx+dy*dy+dz*dz without FMA; neighbour order and the
 # eigen-solver restatement are only bit-comparable with it if the GPU does not fuse either.

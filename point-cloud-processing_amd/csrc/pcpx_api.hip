@@ -1,8 +1,9 @@
-// pcpx_api.hip -- the extern "C" boundary declared in include/pcpx.h (and its companion include/pcpx_radius.h).
+// pcpx_api.hip -- the extern "C" boundary declared in include/pcpx.h (and its companions include/pcpx_radius.h and include/pcpx_features.h).
 // Host-pointer entry points stage through device buffers and are synchronous; *_dev entry points
 // enqueue on the index's stream.  No CPU fallback exists: every compute call needs a HIP device.
 #include "pcpx_internal.h"
 #include "pcpx_radius.h"
+#include "pcpx_features.h"
 
 #include <algorithm>
 #include <cstring>
@@ -1292,6 +1293,34 @@ int pcpx_range_neighbourhoods_self(pcpx_index* h, float radius, float* opt_norma
     });
 }
 
+// The batch forms' spheres: checked (every radius >= 0), then on the device (dq, dr: the caller's, alive until its launch is
+// enqueued) and prepared as queries; nq > 0
+static int check_spheres(const char* what, const float* q_xyz, const float* radii, float radius, u64 nq)
+{
+    if (nq > 0 && !q_xyz) return PCPX_ERR_INVALID;
+    if (radii) {
+        for (u64 i = 0; i < nq; ++i)
+            if (!(radii[i] >= 0.f)) {
+                set_error("%s: radius %llu must be >= 0 (got %g)", what, static_cast<unsigned long long>(i), static_cast<double>(radii[i]));
+                return PCPX_ERR_INVALID;
+            }
+    } else {
+        return check_radius(what, radius);
+    }
+    return PCPX_OK;
+}
+static int upload_spheres(Index* ix, const float* q_xyz, const float* radii, u64 nq, DevBuf& dq, DevBuf& dr, QueryView& qv)
+{
+    int st;
+    if ((st = dq.alloc(nq * 3 * sizeof(float))) != PCPX_OK) return st;
+    if ((st = upload_pageable(dq.p, q_xyz, nq * 3 * sizeof(float), ix->stream)) != PCPX_OK) return st;
+    if (radii) {
+        if ((st = dr.alloc(nq * sizeof(float))) != PCPX_OK) return st;
+        if ((st = upload_pageable(dr.p, radii, nq * sizeof(float), ix->stream)) != PCPX_OK) return st;
+    }
+    return prepare_queries(*ix, dq.as<float>(), nq, qv);
+}
+
 int pcpx_range_neighbourhoods_batch(pcpx_index* h, const float* q_xyz, const float* radii, float radius, uint64_t nq,
                                     float* opt_normals, float* opt_centroids, float* opt_mean_dist, uint32_t* opt_count)
 {
@@ -1302,31 +1331,113 @@ int pcpx_range_neighbourhoods_batch(pcpx_index* h, const float* q_xyz, const flo
         set_error("%s: every output is NULL", what);
         return PCPX_ERR_INVALID;
     }
-    if (nq > 0 && !q_xyz) return PCPX_ERR_INVALID;
-    if (radii) {
-        for (u64 i = 0; i < nq; ++i)
-            if (!(radii[i] >= 0.f)) {
-                set_error("%s: radius %llu must be >= 0 (got %g)", what, static_cast<unsigned long long>(i), static_cast<double>(radii[i]));
-                return PCPX_ERR_INVALID;
-            }
-    } else if ((st = check_radius(what, radius)) != PCPX_OK) {
-        return st;
-    }
+    if ((st = check_spheres(what, q_xyz, radii, radius, nq)) != PCPX_OK) return st;
     if (nq == 0) return PCPX_OK;
     DevBuf dq(ix->pool), dr(ix->pool);
-    if ((st = dq.alloc(nq * 3 * sizeof(float))) != PCPX_OK) return st;
-    if ((st = upload_pageable(dq.p, q_xyz, nq * 3 * sizeof(float), ix->stream)) != PCPX_OK) return st;
-    if (radii) {
-        if ((st = dr.alloc(nq * sizeof(float))) != PCPX_OK) return st;
-        if ((st = upload_pageable(dr.p, radii, nq * sizeof(float), ix->stream)) != PCPX_OK) return st;
-    }
     QueryView qv;
-    if ((st = prepare_queries(*ix, dq.as<float>(), nq, qv)) != PCPX_OK) return st;
+    if ((st = upload_spheres(ix, q_xyz, radii, nq, dq, dr, qv)) != PCPX_OK) return st;
     return moments_to_host(ix, nq, MomentsHost{opt_normals, opt_centroids, opt_mean_dist, opt_count},
                            [&](float* dn, float* dc, float* dm, u32* dk) {
                                return launch_range_moments(*ix, qv, false, 0, (nq + GROUP - 1) / GROUP, radius, dr.as<float>(), dn, dc,
                                                            dm, dk);
                            });
+    });
+}
+
+// ---- local shape features (include/pcpx_features.h): the features form of the sphere walk -------------------------------------------
+struct FeaturesPtrs {
+    float* evals;
+    float* curvature;
+    float* normals;
+    float* axes;
+    uint32_t* count;
+    bool none() const { return !evals && !curvature && !normals && !axes && !count; }
+};
+static int check_features_outputs(const char* what, const FeaturesPtrs& out)
+{
+    if (!out.none()) return PCPX_OK;
+    set_error("%s: every output is NULL", what);
+    return PCPX_ERR_INVALID;
+}
+
+int pcpx_shape_features_self_dev(pcpx_index* h, float radius, uint64_t sorted_first, uint64_t sorted_count, float* d_opt_evals,
+                                 float* d_opt_curvature, float* d_opt_normals, float* d_opt_axes, uint32_t* d_opt_count)
+{
+    static const char* what = "pcpx_shape_features_self_dev";
+    return on_index(h, what, WHOLE_CLOUD, [&](Index* ix) -> int {
+    int st;
+    if ((st = check_features_outputs(what, FeaturesPtrs{d_opt_evals, d_opt_curvature, d_opt_normals, d_opt_axes, d_opt_count})) != PCPX_OK)
+        return st;
+    if ((st = check_radius(what, radius)) != PCPX_OK) return st;
+    if ((st = check_slice(what, sorted_first)) != PCPX_OK) return st;
+    const Slice sl = slice_of(*ix, sorted_first, sorted_count);
+    if (sl.lo == 0 && sl.hi == ix->n && ix->n != ix->n_in) {  // the whole curve order: the rows of the points outside the grid too
+        if ((st = ensure_gather_arrays(*ix, sizeof(u32))) != PCPX_OK) return st;
+        if ((st = launch_range_features_empty_rows(*ix, ix->d_pos_of, ix->n_in, d_opt_evals, d_opt_curvature, d_opt_normals, d_opt_axes,
+                                                   d_opt_count)) != PCPX_OK)
+            return st;
+    }
+    QueryView qv = self_view(*ix);
+    qv.pos_lo = static_cast<u32>(sl.lo);
+    qv.pos_hi = static_cast<u32>(sl.hi);
+    return launch_range_features(*ix, qv, true, sl.gf, sl.gc, radius, nullptr, d_opt_evals, d_opt_curvature, d_opt_normals, d_opt_axes,
+                                 d_opt_count);
+    });
+}
+
+// Host outputs: one device block per asked output, then the copies back
+static int features_to_host(Index* ix, u64 rows, const FeaturesPtrs& out, const std::function<int(const FeaturesPtrs&)>& run)
+{
+    int st;
+    DevBuf de(ix->pool), dv(ix->pool), dn(ix->pool), da(ix->pool), dk(ix->pool);
+    if (out.evals && (st = de.alloc(rows * 3 * sizeof(float))) != PCPX_OK) return st;
+    if (out.curvature && (st = dv.alloc(rows * sizeof(float))) != PCPX_OK) return st;
+    if (out.normals && (st = dn.alloc(rows * 3 * sizeof(float))) != PCPX_OK) return st;
+    if (out.axes && (st = da.alloc(rows * 3 * sizeof(float))) != PCPX_OK) return st;
+    if (out.count && (st = dk.alloc(rows * sizeof(u32))) != PCPX_OK) return st;
+    if ((st = run(FeaturesPtrs{de.as<float>(), dv.as<float>(), dn.as<float>(), da.as<float>(), dk.as<u32>()})) != PCPX_OK) return st;
+    if (out.evals) PCPX_HIP(hipMemcpyAsync(out.evals, de.p, rows * 3 * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+    if (out.curvature) PCPX_HIP(hipMemcpyAsync(out.curvature, dv.p, rows * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+    if (out.normals) PCPX_HIP(hipMemcpyAsync(out.normals, dn.p, rows * 3 * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+    if (out.axes) PCPX_HIP(hipMemcpyAsync(out.axes, da.p, rows * 3 * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+    if (out.count) PCPX_HIP(hipMemcpyAsync(out.count, dk.p, rows * sizeof(u32), hipMemcpyDeviceToHost, ix->stream));
+    PCPX_HIP(hipStreamSynchronize(ix->stream));
+    return PCPX_OK;
+}
+
+int pcpx_shape_features_self(pcpx_index* h, float radius, float* opt_evals, float* opt_curvature, float* opt_normals, float* opt_axes,
+                             uint32_t* opt_count)
+{
+    static const char* what = "pcpx_shape_features_self";
+    return on_index(h, what, WHOLE_CLOUD, [&](Index* ix) -> int {
+    int st;
+    const FeaturesPtrs out{opt_evals, opt_curvature, opt_normals, opt_axes, opt_count};
+    if ((st = check_features_outputs(what, out)) != PCPX_OK) return st;
+    if ((st = check_radius(what, radius)) != PCPX_OK) return st;
+    if (ix->n_in == 0) return PCPX_OK;
+    return features_to_host(ix, ix->n_in, out, [&](const FeaturesPtrs& d) {
+        return pcpx_shape_features_self_dev(h, radius, 0, UINT64_MAX, d.evals, d.curvature, d.normals, d.axes, d.count);
+    });
+    });
+}
+
+int pcpx_shape_features_batch(pcpx_index* h, const float* q_xyz, const float* radii, float radius, uint64_t nq, float* opt_evals,
+                              float* opt_curvature, float* opt_normals, float* opt_axes, uint32_t* opt_count)
+{
+    static const char* what = "pcpx_shape_features_batch";
+    return on_index(h, what, WHOLE_CLOUD, [&](Index* ix) -> int {
+    int st;
+    const FeaturesPtrs out{opt_evals, opt_curvature, opt_normals, opt_axes, opt_count};
+    if ((st = check_features_outputs(what, out)) != PCPX_OK) return st;
+    if ((st = check_spheres(what, q_xyz, radii, radius, nq)) != PCPX_OK) return st;
+    if (nq == 0) return PCPX_OK;
+    DevBuf dq(ix->pool), dr(ix->pool);
+    QueryView qv;
+    if ((st = upload_spheres(ix, q_xyz, radii, nq, dq, dr, qv)) != PCPX_OK) return st;
+    return features_to_host(ix, nq, out, [&](const FeaturesPtrs& d) {
+        return launch_range_features(*ix, qv, false, 0, (nq + GROUP - 1) / GROUP, radius, dr.as<float>(), d.evals, d.curvature, d.normals,
+                                     d.axes, d.count);
+    });
     });
 }
 

@@ -53,8 +53,11 @@ __device__ __forceinline__ float eig_hypot(float x, float y)
     return p * sqrtf(1.f + qp * qp);
 }
 
+// AXIS: also the column of the largest eigenvalue after the ascending sort (column 2) in axis[3] -- the principal axis of the
+// shape features (pcpx_range.hip, k_range_features); the default form is what every other caller compiles.
+template <bool AXIS = false>
 __device__ void eig3_smallest(float a00, float a10, float a20, float a11, float a21, float a22, float normal[3],
-                              float evals[3])
+                              float evals[3], float* axis = nullptr)
 {
     float scale = fmaxf(fmaxf(fmaxf(fabsf(a00), fabsf(a10)), fmaxf(fabsf(a20), fabsf(a11))),
                         fmaxf(fabsf(a21), fabsf(a22)));
@@ -172,6 +175,7 @@ __device__ void eig3_smallest(float a00, float a10, float a20, float a11, float 
     if (l1 <= l0 && l1 <= l2) { nx = q01; ny = q11; nz = q21; }
     if (l2 <= l0 && l2 <= l1) { nx = q02; ny = q12; nz = q22; }
     normal[0] = nx; normal[1] = ny; normal[2] = nz;
+    if constexpr (AXIS) { axis[0] = q02; axis[1] = q12; axis[2] = q22; }
 }
 
 }  // namespace

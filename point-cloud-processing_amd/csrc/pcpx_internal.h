@@ -428,6 +428,12 @@ int launch_range_moments(Index& ix, const QueryView& qv, bool self, u64 group_fi
                          float* d_normals, float* d_centroids, float* d_mean_dist, u32* d_count);
 int launch_range_moments_empty_rows(Index& ix, const u32* d_pos_of, u64 n_rows, float* d_normals, float* d_centroids, float* d_mean_dist,
                                     u32* d_count);
+// the features form (eigenvalues, surface variation, normal, principal axis, count per sphere; any output may be nullptr) and its
+// empty-set values, as the two above
+int launch_range_features(Index& ix, const QueryView& qv, bool self, u64 group_first, u64 group_count, float radius, const float* d_radii,
+                          float* d_evals, float* d_curvature, float* d_normals, float* d_axes, u32* d_count);
+int launch_range_features_empty_rows(Index& ix, const u32* d_pos_of, u64 n_rows, float* d_evals, float* d_curvature, float* d_normals,
+                                     float* d_axes, u32* d_count);
 int launch_aabb_count(Index& ix, const float* d_boxes6, u64 nb, u32* d_out_cnt);
 int launch_aabb_fill(Index& ix, const float* d_boxes6, u64 nb, const u64* d_offsets, u32* d_out_idx);
 int launch_normals(Index& ix, const u32* d_nbr, const u32* d_cnt, const u32* d_rowmap, u64 first, u64 count, u32 k,

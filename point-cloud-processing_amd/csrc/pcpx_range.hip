@@ -30,7 +30,48 @@ constexpr int PRIO_BASE = 1, PRIO_DENSE = 0;
 //
 // MOM (moments form): 1 = per lane the count n, S = sum d and Q = sum d d^T of d = p - q (q: the sphere's
 // centre), then centroid q + S / n and the PCA normal of C = Q - S S^T / n (eig3_smallest, as k_knn and k_normals); 2 = also
-// D = sum |d| for the mean distance D / n.  Lane-per-range leaves only (a packed leaf would need a cross-lane sum of ~11 values).
+// D = sum |d| for the mean distance D / n; 3 = the moments of 1 and the shape features of C: its three
+// eigenvalues, the surface variation and the principal axis beside the normal, out of the one solve.  Lane-per-range leaves only
+// (a packed leaf would need a cross-lane sum of ~11 values).
+struct FeaturesOut {
+    float* evals = nullptr;      // rows x 3, ascending
+    float* curvature = nullptr;  // rows: max(l0, 0) / ((l0 + l1) + l2)
+    float* normals = nullptr;    // rows x 3
+    float* axes = nullptr;       // rows x 3
+    u32* count = nullptr;        // rows
+};
+// what the features form writes for an empty neighbourhood (C = 0), and what its epilogue writes from C and n
+__device__ __forceinline__ void write_features(const FeaturesOut& fo, const u64 row, const u32 cnt, float c00, float c10, float c20, float c11,
+                                               float c21, float c22)
+{
+    if (fo.evals || fo.curvature || fo.normals || fo.axes) {
+        float nrm[3], ev[3], ax[3];
+        eig3_smallest<true>(c00, c10, c20, c11, c21, c22, nrm, ev, ax);
+        const u64 r3 = 3ull * row;
+        if (fo.evals) {
+            fo.evals[r3] = ev[0];
+            fo.evals[r3 + 1] = ev[1];
+            fo.evals[r3 + 2] = ev[2];
+        }
+        if (fo.curvature) {
+            const float sum = (ev[0] + ev[1]) + ev[2];
+            float sv = sum > 0.f ? fmaxf(ev[0], 0.f) / sum : 0.f;  // (n = 1, copies of one point: C = 0)
+            if (cnt == 0u) sv = __builtin_nanf("");
+            fo.curvature[row] = sv;
+        }
+        if (fo.normals) {
+            fo.normals[r3] = nrm[0];
+            fo.normals[r3 + 1] = nrm[1];
+            fo.normals[r3 + 2] = nrm[2];
+        }
+        if (fo.axes) {
+            fo.axes[r3] = ax[0];
+            fo.axes[r3 + 1] = ax[1];
+            fo.axes[r3 + 2] = ax[2];
+        }
+    }
+    if (fo.count) fo.count[row] = cnt;
+}
 struct MomentsOut {
     float* normals = nullptr;    // rows x 3
     float* centroids = nullptr;  // rows x 3
@@ -41,7 +82,7 @@ template <bool SELF, bool FILL, int MOM = 0>
 __device__ __forceinline__ void range_group(const TreeView& t, const QueryView& qv, const u32 g, const float radius,
                                             const float* __restrict__ radii, u32* __restrict__ out_cnt,
                                             const u64* __restrict__ offsets, u32* __restrict__ out_idx, float4* __restrict__ pub,
-                                            const u32 lane, const MomentsOut mo = MomentsOut{})
+                                            const u32 lane, const MomentsOut mo = MomentsOut{}, const FeaturesOut fo = FeaturesOut{})
 {
     static_assert(MOM == 0 || !FILL, "the moments form lists nothing");
     const u32 p = g * GROUP + lane;
@@ -161,6 +202,13 @@ __device__ __forceinline__ void range_group(const TreeView& t, const QueryView& 
         // the centroid and the mean distance (0 / 0), as pcp::estimate_normal and average_distances_to_neighbors do
         const float fn = static_cast<float>(cnt);
         const float m0 = s0 / fn, m1 = s1 / fn, m2 = s2 / fn;
+        if constexpr (MOM == 3) {
+            const bool any = cnt != 0u;
+            const float c00 = any ? q00 - s0 * m0 : 0.f, c10 = any ? q10 - s1 * m0 : 0.f, c11 = any ? q11 - s1 * m1 : 0.f;
+            const float c20 = any ? q20 - s2 * m0 : 0.f, c21 = any ? q21 - s2 * m1 : 0.f, c22 = any ? q22 - s2 * m2 : 0.f;
+            write_features(fo, row, cnt, c00, c10, c20, c11, c21, c22);
+            return;
+        }
         const u64 r3 = 3ull * row;
         if (mo.normals) {
             const bool any = cnt != 0u;
@@ -231,6 +279,26 @@ __global__ __launch_bounds__(256) void k_range_moments_empty_rows(const u32* __r
     }
     if (mo.mean_dist) mo.mean_dist[i] = nan;
     if (mo.count) mo.count[i] = 0u;
+}
+
+// The features form: the walk and the moments of k_range_moments<SELF, 1>, the epilogue's one solve giving the
+// eigenvalues, the surface variation and the principal axis beside the normal
+template <bool SELF>
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void k_range_features(TreeView t, QueryView qv, u32 group_first, u32 group_end, float radius,
+                                                                        const float* __restrict__ radii, FeaturesOut fo)
+{
+    const u32 lane = threadIdx.x & 63u;
+    const u32 g = group_first + virtual_block() * WAVES_PER_BLOCK + wave_in_block();
+    if (g >= group_end) return;
+    range_group<SELF, false, 3>(t, qv, g, radius, radii, nullptr, nullptr, nullptr, nullptr, lane, MomentsOut{}, fo);
+}
+
+// the empty-set values at the rows of the points that are not indexed, as k_range_moments_empty_rows
+__global__ __launch_bounds__(256) void k_range_features_empty_rows(const u32* __restrict__ pos_of, u64 n_rows, FeaturesOut fo)
+{
+    const u64 i = blockIdx.x * static_cast<u64>(blockDim.x) + threadIdx.x;
+    if (i >= n_rows || pos_of[i] != 0xFFFFFFFFu) return;
+    write_features(fo, i, 0u, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f);  // (what the epilogue gives for n = 0)
 }
 
 // AABB ranges: one wave per 64 boxes, no spatial coherence assumed (boxes are few in practice:
@@ -540,6 +608,41 @@ int launch_range_moments_empty_rows(Index& ix, const u32* d_pos_of, u64 n_rows, 
     mo.count = d_count;
     k_range_moments_empty_rows<<<static_cast<u32>((n_rows + 255) / 256), 256, 0, ix.stream>>>(d_pos_of, n_rows, mo);
     return check_hip(hipGetLastError(), "k_range_moments_empty_rows launch", __FILE__, __LINE__);
+}
+
+// The features form, as launch_range_moments / launch_range_moments_empty_rows
+static FeaturesOut features_out(float* d_evals, float* d_curvature, float* d_normals, float* d_axes, u32* d_count)
+{
+    FeaturesOut fo;
+    fo.evals = d_evals;
+    fo.curvature = d_curvature;
+    fo.normals = d_normals;
+    fo.axes = d_axes;
+    fo.count = d_count;
+    return fo;
+}
+
+int launch_range_features(Index& ix, const QueryView& qv, bool self, u64 group_first, u64 group_count, float radius, const float* d_radii,
+                          float* d_evals, float* d_curvature, float* d_normals, float* d_axes, u32* d_count)
+{
+    if (group_count == 0) return PCPX_OK;
+    const u32 grid = grid_for_groups(group_count);
+    const u32 gf = static_cast<u32>(group_first), ge = static_cast<u32>(group_first + group_count);
+    const FeaturesOut fo = features_out(d_evals, d_curvature, d_normals, d_axes, d_count);
+    const dim3 block(64 * WAVES_PER_BLOCK);
+    ProfileScope prof(ix, PCPX_K_RANGE);
+    if (self) k_range_features<true><<<grid, block, 0, ix.stream>>>(ix.view(), qv, gf, ge, radius, d_radii, fo);
+    else k_range_features<false><<<grid, block, 0, ix.stream>>>(ix.view(), qv, gf, ge, radius, d_radii, fo);
+    return check_hip(hipGetLastError(), "k_range_features launch", __FILE__, __LINE__);
+}
+
+int launch_range_features_empty_rows(Index& ix, const u32* d_pos_of, u64 n_rows, float* d_evals, float* d_curvature, float* d_normals,
+                                     float* d_axes, u32* d_count)
+{
+    if (n_rows == 0) return PCPX_OK;
+    const FeaturesOut fo = features_out(d_evals, d_curvature, d_normals, d_axes, d_count);
+    k_range_features_empty_rows<<<static_cast<u32>((n_rows + 255) / 256), 256, 0, ix.stream>>>(d_pos_of, n_rows, fo);
+    return check_hip(hipGetLastError(), "k_range_features_empty_rows launch", __FILE__, __LINE__);
 }
 
 int launch_aabb_count(Index& ix, const float* d_boxes6, u64 nb, u32* d_out_cnt)

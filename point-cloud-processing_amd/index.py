@@ -258,6 +258,48 @@ class Index:
         check(self._lib.pcpx_range_neighbourhoods_self_dev(self._h, float(radius), first, count,
                                                            *(C.c_void_p(d) if d else None for d in (d_normals, d_centroids, d_mean_dist, d_counts))))
 
+    # ---- local shape features (include/pcpx_features.h) ----
+    @staticmethod
+    def _features_outputs(rows, evals, curvature, normals, axes, counts):
+        if not (evals or curvature or normals or axes or counts):
+            raise ValueError("ask for at least one of evals, curvature, normals, axes, counts")
+        return (np.empty((rows, 3), np.float32) if evals else None, np.empty(rows, np.float32) if curvature else None,
+                np.empty((rows, 3), np.float32) if normals else None, np.empty((rows, 3), np.float32) if axes else None,
+                np.empty(rows, np.uint32) if counts else None)
+
+    def shape_features_self(self, radius, evals=True, curvature=True, normals=False, axes=False, counts=False):
+        """Per indexed point, over every point within `radius` (itself included, the neighbourhood of range_neighbourhoods_self):
+        the three eigenvalues of the centred scatter matrix (n x 3, ascending, not divided by the count), the surface variation
+        max(l0, 0) / (l0 + l1 + l2) (n; the `curvature` that Index.segment gates on), the PCA normal (n x 3, bit for bit that of
+        range_neighbourhoods_self), the principal axis (n x 3: the largest eigenvalue's eigenvector) and the count (n), in input
+        order.  Returns the asked outputs in that order (one array alone when one is asked).  An empty neighbourhood (a point
+        outside the voxel grid): eigenvalues 0, curvature NaN, normal and axis (0, 0, 1), count 0."""
+        outs = self._features_outputs(self.n_in, evals, curvature, normals, axes, counts)
+        check(self._lib.pcpx_shape_features_self(self._h, float(radius), *(_vp(o) for o in outs)))
+        return self._moments_result(outs)
+
+    def shape_features(self, queries, radius, evals=True, curvature=True, normals=False, axes=False, counts=False):
+        """The same for arbitrary spheres: centres `queries` (m x 3), `radius` a scalar or one radius per sphere."""
+        q = _f32(queries, 3)
+        radii = None
+        r = 0.0
+        if np.ndim(radius) == 0:
+            r = float(radius)
+        else:
+            radii = _f32(radius).reshape(-1)
+            if len(radii) != len(q):
+                raise ValueError("one radius per sphere")
+        outs = self._features_outputs(len(q), evals, curvature, normals, axes, counts)
+        check(self._lib.pcpx_shape_features_batch(self._h, _vp(q), _vp(radii), r, len(q), *(_vp(o) for o in outs)))
+        return self._moments_result(outs)
+
+    def shape_features_self_dev(self, radius, d_evals=None, d_curvature=None, d_normals=None, d_axes=None, d_counts=None, first=0,
+                                count=_capi.UINT64_MAX):
+        """Device form (pointers to device arrays by input row; any may be None, not all), enqueued on the index's stream: the rows of
+        the curve positions [first, first + count) -- plus, when that is the whole order, the rows of points outside the grid."""
+        check(self._lib.pcpx_shape_features_self_dev(self._h, float(radius), first, count,
+                                                     *(C.c_void_p(d) if d else None for d in (d_evals, d_curvature, d_normals, d_axes, d_counts))))
+
     # ---- clustering (include/pcpx_cluster.h) ----
     def cluster(self, radius, min_pts=1, compact=True, want_core=False, want_counts=False):
         """Radius-connected components (min_pts = 1) or DBSCAN of the indexed cloud: two points are joined iff one is in the other's
