@@ -243,6 +243,17 @@ FEATURES_SIGNATURES = {
                                             C.c_void_p, C.c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/pcpx_keypoints.h (local maxima over a radius, ISS keypoints)
+KEYPOINTS_SIGNATURES = {
+    "pcpx_local_maxima_self_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    "pcpx_local_maxima_self": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, u64p]),
+    "pcpx_iss_keypoints_self_dev": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcpx_iss_keypoints_self": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                          u64p, C.c_void_p]),
+}
+
 
 def load():
     """Load libpcpx.so; raises if it has not been built (run __graft_entry__.build())."""
@@ -256,7 +267,8 @@ def load():
     _share_hip_runtime_with_torch()
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(RADIUS_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items())\
-            + list(SUBSAMPLE_SIGNATURES.items()) + list(SEGMENT_SIGNATURES.items()) + list(FEATURES_SIGNATURES.items()):
+            + list(SUBSAMPLE_SIGNATURES.items()) + list(SEGMENT_SIGNATURES.items()) + list(FEATURES_SIGNATURES.items())\
+            + list(KEYPOINTS_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -412,6 +412,67 @@ class Index:
                                                 *(C.c_void_p(d) if d else None for d in (d_owner, d_kept_rows, d_kept_count)), C.byref(rounds)))
         return int(rounds.value)
 
+    # ---- keypoints (include/pcpx_keypoints.h) ----
+    @staticmethod
+    def _dptr(d):
+        """a device array as the C ABI takes it: None, an address, or anything with data_ptr() (a torch tensor)"""
+        if d is None:
+            return None
+        addr = d.data_ptr() if hasattr(d, "data_ptr") else int(d)
+        return C.c_void_p(addr) if addr else None
+
+    def _kept_result(self, kept, count, keep, want_keep, extra=None):
+        out = (kept[:int(count.value)].copy(),)
+        if want_keep:
+            out += (keep.astype(bool),)
+        if extra is not None:
+            out += (extra,)
+        return out[0] if len(out) == 1 else out
+
+    def local_maxima(self, score, radius, min_score=float("-inf"), min_neighbours=1, want_keep=False):
+        """Sphere-wise non-maximum suppression: the points that are the maxima of `score` (n_in, float32) over `radius`.  A point is
+        kept iff it is indexed, its score is not NaN and >= min_score, no other indexed point j in its sphere (the rule of
+        range_count_self) beats it -- score_j > score_i, or score_j == score_i and j < i -- and its sphere holds at least
+        min_neighbours points, itself included.  No two kept points are within `radius`; a dropped point need not have a kept one
+        nearby (subsample promises that, this does not).  Minima: negate the score.
+        Returns the kept input indices, ascending (uint32)[, the keep mask bool (n_in,)]."""
+        s = _f32(score).reshape(-1)
+        if len(s) != self.n_in:
+            raise ValueError("one score per input point")
+        keep = np.empty(self.n_in, np.uint8)
+        kept = np.empty(self.n_in, np.uint32)
+        count = C.c_uint64(0)
+        check(self._lib.pcpx_local_maxima_self(self._h, _vp(s), float(radius), float(min_score), int(min_neighbours), 0, _vp(keep), _vp(kept),
+                                               C.byref(count)))
+        return self._kept_result(kept, count, keep, want_keep)
+
+    def local_maxima_dev(self, d_score, radius, d_keep, min_score=float("-inf"), min_neighbours=1, d_kept_rows=None, d_kept_count=None):
+        """Device form (torch tensors or pointers to device arrays: score float32 and keep uint8 by input row, kept_rows uint32 with
+        room for n_in entries, d_kept_count one uint64), enqueued on the index's stream with no synchronisation: a curvature or
+        saliency that shape_features_self_dev or iss_keypoints_dev left on the device goes straight in."""
+        check(self._lib.pcpx_local_maxima_self_dev(self._h, self._dptr(d_score), float(radius), float(min_score), int(min_neighbours), 0,
+                                                   *(self._dptr(d) for d in (d_keep, d_kept_rows, d_kept_count))))
+
+    def iss_keypoints(self, salient_radius, non_max_radius, gamma21=0.975, gamma32=0.975, min_neighbours=5, want_saliency=False,
+                      want_keep=False):
+        """ISS keypoints (Zhong 2009) of the indexed cloud: with l0 <= l1 <= l2 and count of shape_features_self(salient_radius), the
+        saliency of a point is l0 / count where l1 < gamma21 l2 and l0 < gamma32 l1 and NaN elsewhere (and outside the voxel grid);
+        the keypoints are local_maxima(saliency, non_max_radius, min_neighbours=min_neighbours).
+        Returns the kept input indices, ascending (uint32)[, the keep mask bool (n_in,)][, the saliency float32 (n_in,)]."""
+        keep = np.empty(self.n_in, np.uint8)
+        kept = np.empty(self.n_in, np.uint32)
+        saliency = np.empty(self.n_in, np.float32) if want_saliency else None
+        count = C.c_uint64(0)
+        check(self._lib.pcpx_iss_keypoints_self(self._h, float(salient_radius), float(non_max_radius), float(gamma21), float(gamma32),
+                                                int(min_neighbours), 0, _vp(keep), _vp(kept), C.byref(count), _vp(saliency)))
+        return self._kept_result(kept, count, keep, want_keep, saliency)
+
+    def iss_keypoints_dev(self, salient_radius, non_max_radius, d_keep, gamma21=0.975, gamma32=0.975, min_neighbours=5, d_kept_rows=None,
+                          d_kept_count=None, d_saliency=None):
+        """Device form (as local_maxima_dev; d_saliency float32 by input row), enqueued on the index's stream with no synchronisation."""
+        check(self._lib.pcpx_iss_keypoints_self_dev(self._h, float(salient_radius), float(non_max_radius), float(gamma21), float(gamma32),
+                                                    int(min_neighbours), 0, *(self._dptr(d) for d in (d_keep, d_kept_rows, d_kept_count, d_saliency))))
+
     # ---- normals ----
     def normals_knn_self(self, k, eps=1e-5, want_knn=False):
         nrm = np.empty((self.n_in, 3), np.float32)
