@@ -253,6 +253,11 @@ KEYPOINTS_SIGNATURES = {
     "pcpx_iss_keypoints_self": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                           u64p, C.c_void_p]),
 }
+# name -> (restype, argtypes); every symbol declared in include/pcpx_descriptors.h (FPFH descriptors)
+DESCRIPTORS_SIGNATURES = {
+    "pcpx_fpfh_self_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcpx_fpfh_self": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
 
 
 def load():
@@ -268,7 +273,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(RADIUS_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items())\
             + list(SUBSAMPLE_SIGNATURES.items()) + list(SEGMENT_SIGNATURES.items()) + list(FEATURES_SIGNATURES.items())\
-            + list(KEYPOINTS_SIGNATURES.items()):
+            + list(KEYPOINTS_SIGNATURES.items()) + list(DESCRIPTORS_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

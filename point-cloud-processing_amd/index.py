@@ -473,6 +473,34 @@ class Index:
         check(self._lib.pcpx_iss_keypoints_self_dev(self._h, float(salient_radius), float(non_max_radius), float(gamma21), float(gamma32),
                                                     int(min_neighbours), 0, *(self._dptr(d) for d in (d_keep, d_kept_rows, d_kept_count, d_saliency))))
 
+    # ---- descriptors (include/pcpx_descriptors.h) ----
+    def fpfh(self, normals, radius, rows=None, want_spfh=False):
+        """Fast Point Feature Histograms (Rusu et al. 2009) over `radius` from `normals` (n_in x 3, float32, used as given): 33 floats
+        per described point -- three blocks of 11 bins (the angle of the target's normal about the source's, the v component of the
+        target's normal, the source's normal along the line), each scaled to sum 100 -- the 1 / d^2-weighted sum of the neighbours'
+        simplified histograms.  rows: distinct input indices to describe (default: every input row); a row outside the voxel grid or
+        >= n_in gets zeros.
+        Returns fpfh float32 (m, 33)[, spfh float32 (n_in, 33), pairs uint32 (n_in,): by input row, and with `rows` zero except at
+        the points that some described row's sphere holds]."""
+        nrm = _f32(normals).reshape(-1)
+        if len(nrm) != 3 * self.n_in:
+            raise ValueError("one normal per input point")
+        sel = None if rows is None else np.ascontiguousarray(rows, np.uint32).reshape(-1)
+        m = self.n_in if sel is None else len(sel)
+        out = np.empty((m, 33), np.float32)
+        spfh = np.empty((self.n_in, 33), np.float32) if want_spfh else None
+        pairs = np.empty(self.n_in, np.uint32) if want_spfh else None
+        held = sel if sel is None or len(sel) else np.zeros(1, np.uint32)  # (an empty selection still passes an address: NULL means every row)
+        check(self._lib.pcpx_fpfh_self(self._h, _vp(nrm), float(radius), _vp(held), 0 if sel is None else m, 0, _vp(out), _vp(spfh), _vp(pairs)))
+        return (out, spfh, pairs) if want_spfh else out
+
+    def fpfh_dev(self, d_normals, radius, d_fpfh, d_rows=None, m=0, d_spfh=None, d_pairs=None):
+        """Device form (torch tensors or pointers to device arrays: normals float32 (n_in, 3); rows uint32, m of them -- the kept rows
+        that iss_keypoints_dev left on the device go straight in; fpfh float32 (m, 33), or (n_in, 33) without rows; spfh float32
+        (n_in, 33) and pairs uint32 (n_in,)), enqueued on the index's stream with no synchronisation."""
+        check(self._lib.pcpx_fpfh_self_dev(self._h, self._dptr(d_normals), float(radius), self._dptr(d_rows), int(m) if d_rows is not None else 0, 0,
+                                           *(self._dptr(d) for d in (d_fpfh, d_spfh, d_pairs))))
+
     # ---- normals ----
     def normals_knn_self(self, k, eps=1e-5, want_knn=False):
         nrm = np.empty((self.n_in, 3), np.float32)
