@@ -34,9 +34,12 @@
 // Arithmetic follows the reference exactly: d = p - q, dx*dx + dy*dy + dz*dz in float32 without
 // FMA contraction (include/pcp/common/norm.hpp:102-112), eps-box exclusion
 // (include/pcp/common/vector3d_queries.hpp:47-64).  The box lower bound is monotone in float, so
-// pruning never changes the result.  Rows are the exact k nearest in ascending (d2, index) order; if
-// several points tie EXACTLY with the k-th distance, which of them is kept is unspecified -- as in the
-// reference, where it depends on heap order (linked_octree_node.hpp:479-489, linked_kdtree.hpp:483-488).
+// pruning never changes the result; k_knn's node tests use the bound with its sum of squares fused into three FMAs, which can
+// exceed the unfused one by an ulp, against a tau slackened by more than that (pcpx_box_bound.h: the derivation) -- a node that
+// holds a point with d2 <= tau is still never pruned, and tau and the candidate tests stay exact.  Rows are the exact k nearest
+// in ascending (d2, index) order; if several points tie EXACTLY with the k-th distance, which of them is kept is unspecified --
+// as in the reference, where it depends on heap order (linked_octree_node.hpp:479-489, linked_kdtree.hpp:483-488).
+#include "pcpx_box_bound.h"
 #include "pcpx_device.h"
 #include "pcpx_eig3.h"
 
@@ -626,7 +629,8 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
     constexpr int packed_free = KCAP <= 16 ? PACKED_FREE16 : 0;  // (see PACKED_FREE16)
     const u32 wa_packed_full = packed_free > 0 ? lds_row0 + (static_cast<u32>(BUF - packed_free + 1) << 9) : wa_full;
 
-    auto need = [&](const NodeBox& b) { return box_d2(b, qx, qy, qz) <= tau; };
+    // (node tests only: the fused bound against the slackened tau, pcpx_box_bound.h; hipcc forms the slackened tau once per expansion)
+    auto need = [&](const NodeBox& b) { return box_bound_fused(b, qx, qy, qz) <= box_bound_tau(tau); };
     // single-pass kernels: the eps-box test waits for the compaction, unless the launcher picked the EPS_EACH form (launch_knn_t)
     const EpsFilter eps_filter{deferred_eps(MULTI, EPS_EACH), eps_thr, eps, qx, qy, qz, t.leaves};
 
