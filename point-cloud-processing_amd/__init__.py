@@ -3,8 +3,9 @@
 The compute path is libpcpx.so (hand-written HIP for gfx950, C ABI in include/pcpx.h); importing the
 package does not load it, using any compute entry point does and fails loudly if it is missing.
 """
-from . import ply, simplify, surface, synthetic  # noqa: F401
+from . import match, ply, simplify, surface, synthetic  # noqa: F401
 from ._capi import Grid3d  # noqa: F401
+from .match import match_correspondences, match_correspondences_dev, match_nearest, match_nearest_dev, match_plan  # noqa: F401
 from .simplify import hierarchy_simplification, hierarchy_simplification_dev  # noqa: F401
 from .surface import regular_grid_containing, surface_nets, surface_nets_from_hint  # noqa: F401
 from .filters import bilateral_filter_normals, bilateral_filter_points, wlop  # noqa: F401
@@ -15,4 +16,5 @@ __all__ = ["Index", "LinkedOctree", "LinkedKdTree", "KdTreeK", "PcpxError", "bou
            "estimate_normals", "estimate_normals_batch", "propagate_normal_orientations", "propagate_normal_orientations_dev", "shard_range", "shard_cuts_by_cost", "ply", "synthetic",
            "bilateral_filter_points", "bilateral_filter_normals", "wlop",
            "Grid3d", "regular_grid_containing", "surface_nets", "surface_nets_from_hint", "surface",
-           "hierarchy_simplification", "hierarchy_simplification_dev", "simplify"]
+           "hierarchy_simplification", "hierarchy_simplification_dev", "simplify",
+           "match", "match_nearest", "match_nearest_dev", "match_correspondences", "match_correspondences_dev", "match_plan"]

@@ -258,6 +258,22 @@ DESCRIPTORS_SIGNATURES = {
     "pcpx_fpfh_self_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pcpx_fpfh_self": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
+# name -> (restype, argtypes); every symbol declared in include/pcpx_match.h (descriptor matching)
+PCPX_MATCH_MAX_DIMS = 64
+PCPX_MATCH_NONE = 0xFFFFFFFF
+PCPX_MATCH_SKIP_ZERO_ROWS = 1
+PCPX_MATCH_MUTUAL = 2
+MATCH_SIGNATURES = {
+    "pcpx_match_plan": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32, u32p, u32p, u64p, u64p]),
+    "pcpx_match_nearest_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcpx_match_nearest": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
+    "pcpx_match_correspondences_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_float, C.c_uint32, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcpx_match_correspondences": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_float, C.c_uint32, C.c_int,
+                                             C.c_void_p, C.c_void_p, u64p]),
+}
 
 
 def load():
@@ -273,7 +289,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(RADIUS_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items())\
             + list(SUBSAMPLE_SIGNATURES.items()) + list(SEGMENT_SIGNATURES.items()) + list(FEATURES_SIGNATURES.items())\
-            + list(KEYPOINTS_SIGNATURES.items()) + list(DESCRIPTORS_SIGNATURES.items()):
+            + list(KEYPOINTS_SIGNATURES.items()) + list(DESCRIPTORS_SIGNATURES.items()) + list(MATCH_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args
