@@ -275,6 +275,21 @@ MATCH_SIGNATURES = {
                                              C.c_void_p, C.c_void_p, u64p]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/pcpx_register.h (rigid registration from correspondences)
+PCPX_RANSAC_REFIT = 1
+REGISTER_SIGNATURES = {
+    "pcpx_ransac_plan": (C.c_int, [C.c_uint64, C.c_uint64, u32p, u64p, u64p]),
+    "pcpx_ransac_rigid_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
+                                        C.c_float, C.c_float, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcpx_ransac_rigid": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_float,
+                                    C.c_float, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcpx_rigid_fit_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                     C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcpx_rigid_fit": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int,
+                                 C.c_void_p, C.c_void_p]),
+}
+
 
 def load():
     """Load libpcpx.so; raises if it has not been built (run __graft_entry__.build())."""
@@ -289,7 +304,8 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(RADIUS_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items())\
             + list(SUBSAMPLE_SIGNATURES.items()) + list(SEGMENT_SIGNATURES.items()) + list(FEATURES_SIGNATURES.items())\
-            + list(KEYPOINTS_SIGNATURES.items()) + list(DESCRIPTORS_SIGNATURES.items()) + list(MATCH_SIGNATURES.items()):
+            + list(KEYPOINTS_SIGNATURES.items()) + list(DESCRIPTORS_SIGNATURES.items()) + list(MATCH_SIGNATURES.items())\
+            + list(REGISTER_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -73,6 +73,18 @@ __device__ __forceinline__ NodeBox4 load_node4(const NodeBox* first_child)
     return out;
 }
 
+// the 32-bit finaliser of MurmurHash3: a bijection, so distinct words give distinct keys (pcpx_subsample.h's
+// priorities, pcpx_register.h's sampling)
+__host__ __device__ __forceinline__ u32 fmix32(u32 x)
+{
+    x ^= x >> 16;
+    x *= 0x85EBCA6Bu;
+    x ^= x >> 13;
+    x *= 0xC2B2AE35u;
+    x ^= x >> 16;
+    return x;
+}
+
 __device__ __forceinline__ bool any_lane(bool c) { return __builtin_amdgcn_ballot_w64(c) != 0ull; }
 
 // Index records (leaves, node boxes) are immutable while a query kernel runs.  Reading them through

@@ -8,6 +8,7 @@
 //   k_match_keep    ratio and mutual test, one thread per source; pcpx_scan.h and k_match_compact write the kept pairs
 // The mutual test is the same two kernels with the roles of the sets swapped.
 #include "pcpx_device.h"
+#include "pcpx_lease.h"
 #include "pcpx_match.h"
 #include "pcpx_scan.h"
 
@@ -318,71 +319,6 @@ int correspondences_device(const Layout& L, char* base, const float* d_src, u64 
     return PCPX_OK;
 }
 
-// ---- the scratch of a call that does not wait for its kernels ---------------------------------------------------------------------------
-// A block of the device's pool goes back to the pool when the host knows that nothing queued reads it.  A _dev call returns before
-// that, so it leaves the block here with an event recorded behind its last kernel; the next call of this file on the device gives
-// back the blocks whose events have passed, and takes over a block that its own stream still holds (the stream orders the two calls).
-// Guarded by the device's DeviceShared::mu, which every caller holds.
-struct HeldScratch {
-    hipStream_t stream;
-    void* p;
-    size_t bytes;
-    hipEvent_t passed;
-};
-constexpr int MT_MAX_DEVICES = 64;
-std::vector<HeldScratch> g_held[MT_MAX_DEVICES];
-
-struct ScratchLease {
-    DevPool& pool;
-    std::vector<HeldScratch>& held;
-    hipStream_t stream;
-    void* p = nullptr;
-    size_t bytes = 0;
-    ScratchLease(DeviceShared& sh, int device, hipStream_t s) : pool(sh.pool), held(g_held[device]), stream(s) {}
-    ScratchLease(const ScratchLease&) = delete;
-    ScratchLease& operator=(const ScratchLease&) = delete;
-    int take(size_t need)
-    {
-        bytes = need;
-        for (size_t i = 0; i < held.size();) {
-            HeldScratch& h = held[i];
-            const hipError_t e = hipEventQuery(h.passed);
-            const bool mine = !p && h.stream == stream && h.bytes >= need && h.bytes <= 2 * need + (1u << 20);
-            if (e != hipSuccess) (void)hipGetLastError();  // (hipErrorNotReady)
-            if (e != hipSuccess && !mine) {
-                ++i;
-                continue;
-            }
-            if (mine) p = h.p, bytes = h.bytes;
-            else pool.release(h.p);
-            (void)hipEventDestroy(h.passed);
-            held.erase(held.begin() + static_cast<std::ptrdiff_t>(i));
-        }
-        if (!p) p = pool.acquire(need);
-        return p ? PCPX_OK : PCPX_ERR_ALLOC;
-    }
-    // the call's kernels are queued: the block is given back once the stream has passed this point
-    int leave_queued()
-    {
-        HeldScratch h{stream, p, bytes, nullptr};
-        PCPX_HIP(hipEventCreateWithFlags(&h.passed, hipEventDisableTiming));
-        const hipError_t e = hipEventRecord(h.passed, stream);
-        if (e != hipSuccess) {
-            (void)hipEventDestroy(h.passed);
-            PCPX_HIP(e);
-        }
-        held.push_back(h);
-        p = nullptr;
-        return PCPX_OK;
-    }
-    ~ScratchLease()  // (a host-form call has synchronised its stream; a failed call waits here)
-    {
-        if (!p) return;
-        (void)hipStreamSynchronize(stream);
-        pool.release(p);
-    }
-};
-
 int check_match_args(const char* what, const void* src, u64 m, const void* tgt, u64 n, u32 dims, u32 flags, u32 known_flags, const void* out)
 {
     if (dims == 0 || dims > MT_MAX_DIMS) {
@@ -461,7 +397,7 @@ int pcpx_match_nearest_dev(const float* d_src, uint64_t m, const float* d_tgt, u
     static const char* what = "pcpx_match_nearest_dev";
     int st = check_match_args(what, d_src, m, d_tgt, n, dims, flags, PCPX_MATCH_SKIP_ZERO_ROWS, d_out_idx);
     if (st != PCPX_OK || m == 0) return st;
-    if (device < 0 || device >= MT_MAX_DEVICES) return select_device(device);
+    if (device < 0 || device >= LEASE_MAX_DEVICES) return select_device(device);
     return on_shared(device, what, [&](DeviceShared& sh) -> int {
         const hipStream_t s = static_cast<hipStream_t>(stream);
         const Layout L(m, n, dims);
@@ -481,7 +417,7 @@ int pcpx_match_nearest(const float* src, uint64_t m, const float* tgt, uint64_t 
     static const char* what = "pcpx_match_nearest";
     int st = check_match_args(what, src, m, tgt, n, dims, flags, PCPX_MATCH_SKIP_ZERO_ROWS, out_idx);
     if (st != PCPX_OK || m == 0) return st;
-    if (device < 0 || device >= MT_MAX_DEVICES) return select_device(device);
+    if (device < 0 || device >= LEASE_MAX_DEVICES) return select_device(device);
     return on_shared(device, what, [&](DeviceShared& sh) -> int {
         PooledStream ps;
         PCPX_HIP(pooled_stream_get(&ps.s));
@@ -515,7 +451,7 @@ int pcpx_match_correspondences_dev(const float* d_src, uint64_t m, const float* 
     int st = check_match_args(what, d_src, m, d_tgt, n, dims, flags, PCPX_MATCH_SKIP_ZERO_ROWS | PCPX_MATCH_MUTUAL, d_out_pairs);
     if (st != PCPX_OK || (st = check_ratio(what, max_ratio_sq)) != PCPX_OK) return st;
     if (m == 0 && !d_opt_out_count) return PCPX_OK;
-    if (device < 0 || device >= MT_MAX_DEVICES) return select_device(device);
+    if (device < 0 || device >= LEASE_MAX_DEVICES) return select_device(device);
     return on_shared(device, what, [&](DeviceShared& sh) -> int {
         const hipStream_t s = static_cast<hipStream_t>(stream);
         const Layout L(m, n, dims);
@@ -541,7 +477,7 @@ int pcpx_match_correspondences(const float* src, uint64_t m, const float* tgt, u
     *out_count = 0;
     int st = check_match_args(what, src, m, tgt, n, dims, flags, PCPX_MATCH_SKIP_ZERO_ROWS | PCPX_MATCH_MUTUAL, out_pairs);
     if (st != PCPX_OK || (st = check_ratio(what, max_ratio_sq)) != PCPX_OK || m == 0) return st;
-    if (device < 0 || device >= MT_MAX_DEVICES) return select_device(device);
+    if (device < 0 || device >= LEASE_MAX_DEVICES) return select_device(device);
     return on_shared(device, what, [&](DeviceShared& sh) -> int {
         PooledStream ps;
         PCPX_HIP(pooled_stream_get(&ps.s));

@@ -33,17 +33,6 @@ constexpr u32 ROUND_BATCH = PCPX_SUBSAMPLE_ROUND_BATCH;  // rounds between two r
 __device__ __forceinline__ u32 state_load(const u32* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void state_store(u32* p, u32 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// the 32-bit finaliser of MurmurHash3: a bijection, so the keys of distinct input indices are distinct
-__host__ __device__ __forceinline__ u32 fmix32(u32 x)
-{
-    x ^= x >> 16;
-    x *= 0x85EBCA6Bu;
-    x ^= x >> 13;
-    x *= 0xC2B2AE35u;
-    x ^= x >> 16;
-    return x;
-}
-
 struct States8 {
     u32 v[LEAF];
 };
