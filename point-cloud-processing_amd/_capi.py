@@ -290,6 +290,20 @@ REGISTER_SIGNATURES = {
                                  C.c_void_p, C.c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/pcpx_icp.h (nearest partners under a pose, the ICP loop)
+PCPX_ICP_NONE = 0xFFFFFFFF
+PCPX_ICP_POINT_TO_PLANE = 1
+PCPX_ICP_MAX_ITERATIONS = 1024
+PCPX_ICP_EXHAUSTED, PCPX_ICP_CONVERGED, PCPX_ICP_STARVED, PCPX_ICP_DEGENERATE = range(4)
+ICP_SIGNATURES = {
+    "pcpx_nearest_posed_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "pcpx_nearest_posed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "pcpx_icp_rigid_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcpx_icp_rigid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 
 def load():
     """Load libpcpx.so; raises if it has not been built (run __graft_entry__.build())."""
@@ -305,7 +319,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(RADIUS_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items())\
             + list(SUBSAMPLE_SIGNATURES.items()) + list(SEGMENT_SIGNATURES.items()) + list(FEATURES_SIGNATURES.items())\
             + list(KEYPOINTS_SIGNATURES.items()) + list(DESCRIPTORS_SIGNATURES.items()) + list(MATCH_SIGNATURES.items())\
-            + list(REGISTER_SIGNATURES.items()):
+            + list(REGISTER_SIGNATURES.items()) + list(ICP_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

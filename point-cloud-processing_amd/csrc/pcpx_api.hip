@@ -1020,6 +1020,10 @@ int pcpx_debug_set(pcpx_index* h, const char* name, int64_t value)
         ix->tuning.gather = value != 0;
     } else if (key == "gather_counts") {
         ix->tuning.gather_counts = value != 0;
+    } else if (key == "icp_resort") {
+        ix->tuning.icp_resort = value != 0;
+    } else if (key == "icp_previous_start") {
+        ix->tuning.icp_previous_start = value < 0 ? -1 : value != 0;
     } else {
         set_error("pcpx_debug_set: no setting called '%s'", name);
         return PCPX_ERR_INVALID;

@@ -50,6 +50,20 @@ PCPX_HORN_FN void horn_rotate(double (&a)[4][4], double (&v)[4][4])
     a[P][Q] = a[Q][P] = 0.0;
 }
 
+// the rotation matrix, row-major, of the unit quaternion (qw, qx, qy, qz)
+PCPX_HORN_FN void horn_quaternion_matrix(double qw, double qx, double qy, double qz, double (&r)[9])
+{
+    r[0] = 1.0 - 2.0 * (qy * qy + qz * qz);
+    r[1] = 2.0 * (qx * qy - qw * qz);
+    r[2] = 2.0 * (qx * qz + qw * qy);
+    r[3] = 2.0 * (qx * qy + qw * qz);
+    r[4] = 1.0 - 2.0 * (qx * qx + qz * qz);
+    r[5] = 2.0 * (qy * qz - qw * qx);
+    r[6] = 2.0 * (qx * qz - qw * qy);
+    r[7] = 2.0 * (qy * qz + qw * qx);
+    r[8] = 1.0 - 2.0 * (qx * qx + qy * qy);
+}
+
 // h: H row-major, H[a][b] = sum p_a q_b.  r: the rotation, row-major.  Always a proper rotation (it is a unit quaternion's matrix);
 // the identity for H = 0.
 PCPX_HORN_FN void horn_rotation(const double (&h)[9], double (&r)[9])
@@ -87,15 +101,7 @@ PCPX_HORN_FN void horn_rotation(const double (&h)[9], double (&r)[9])
     } else {
         qw /= norm, qx /= norm, qy /= norm, qz /= norm;
     }
-    r[0] = 1.0 - 2.0 * (qy * qy + qz * qz);
-    r[1] = 2.0 * (qx * qy - qw * qz);
-    r[2] = 2.0 * (qx * qz + qw * qy);
-    r[3] = 2.0 * (qx * qy + qw * qz);
-    r[4] = 1.0 - 2.0 * (qx * qx + qz * qz);
-    r[5] = 2.0 * (qy * qz - qw * qx);
-    r[6] = 2.0 * (qx * qz - qw * qy);
-    r[7] = 2.0 * (qy * qz + qw * qx);
-    r[8] = 1.0 - 2.0 * (qx * qx + qy * qy);
+    horn_quaternion_matrix(qw, qx, qy, qz, r);
 }
 
 }  // namespace pcpx

@@ -261,6 +261,10 @@ struct Index {
                                   // reads are ten million cache lines); a switch, like `gather`
         int gather = 0;           // input-order normals + counts through the gather-form permute (measured round 5: 1-3 % SLOWER than the
                                   // direct scattered stores on the 10 M clouds -- the search kernel is not bound by them; kept as a switch)
+        int icp_resort = 0;       // pcpx_icp.hip: curve-sort the moved source again in every iteration instead of once per call (an A/B
+                                  // switch: the results do not depend on the source order)
+        int icp_previous_start = -1;  // pcpx_icp.hip: from the second round on a lane starts from its previous partner (1), from nothing
+                                      // (0), or as that file's default says (-1); the results are the same
     } tuning;
     int eps_test_mode = 0;  // k_knn's eps-box test: 0 = where it is cheaper (query.hip: eps_box_threshold), 1 = in the compaction, 2 = per candidate
 
@@ -473,6 +477,13 @@ struct HierarchyTimes {
 int hierarchy_device(const float* d_xyz, u64 n, u64 cluster_size, double var_max, hipStream_t s, DevPool& pool, float* d_out_xyz, u32* d_out_idx,
                      u64 capacity, u64* out_count, HierarchyTimes* times = nullptr);
 int launch_invert_perm(const u32* d_perm, u64 n, u32* d_position_of, hipStream_t s);
+// register.hip: the least-squares rigid fit of pcpx_register.h over correspondences [0, min(*d_count, capacity)) of d_pairs ({row of
+// d_p, row of d_q}; d_count null: capacity), enqueued on s -- the kernels, the order of the sums and so the bits of pcpx_rigid_fit_dev.
+// scratch: fit_scratch_bytes().  With fewer than three usable pairs d_out gets d_fallback (16 doubles; null: the identity) and
+// *d_out_rms (optional) NaN.
+size_t fit_scratch_bytes();
+int fit_pairs_device(const float* d_p, u32 np, const float* d_q, u32 nq, const u32* d_pairs, u32 capacity, const u64* d_count, void* d_scratch,
+                     const double* d_fallback, double* d_out, double* d_out_rms, hipStream_t s);
 
 // ---- the runtime (pcpx_runtime.hip) ---------------------------------------------------------------------------------------------
 extern thread_local std::string g_err;  // the thread's error text (pcpx_last_error)

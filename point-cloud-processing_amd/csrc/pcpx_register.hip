@@ -629,6 +629,15 @@ struct Staged {
 
 }  // namespace
 
+size_t fit_scratch_bytes() { return FIT_SCRATCH_BYTES; }
+
+int fit_pairs_device(const float* d_p, u32 np, const float* d_q, u32 nq, const u32* d_pairs, u32 capacity, const u64* d_count, void* d_scratch,
+                     const double* d_fallback, double* d_out, double* d_out_rms, hipStream_t s)
+{
+    const FitSet set{Pairs{d_p, d_q, d_pairs, d_count, np, nq, capacity}, false, nullptr, nullptr, 0u};
+    return fit_device(set, static_cast<char*>(d_scratch), d_fallback, d_out, d_out_rms, s);
+}
+
 }  // namespace pcpx
 
 using namespace pcpx;

@@ -501,6 +501,71 @@ class Index:
         check(self._lib.pcpx_fpfh_self_dev(self._h, self._dptr(d_normals), float(radius), self._dptr(d_rows), int(m) if d_rows is not None else 0, 0,
                                            *(self._dptr(d) for d in (d_fpfh, d_spfh, d_pairs))))
 
+    # ---- iterative closest point (include/pcpx_icp.h) ----
+    @staticmethod
+    def _pose16(pose):
+        if pose is None:
+            return None
+        p = np.ascontiguousarray(pose, dtype=np.float64).reshape(-1)
+        if p.size != 16:
+            raise ValueError("pose must be 4 x 4")
+        return p
+
+    def nearest_posed(self, source, radius, pose=None, want_d2=False):
+        """The exact nearest indexed point of every row of `source` ((m, 3) float32-convertible) moved by `pose` ((4, 4) float64,
+        source -> this cloud; None: the identity) among those within `radius`: the smallest (d2, input index), so ties go to the
+        lowest input index.  Returns partner uint32 (m,) -- 0xFFFFFFFF where there is none -- [, d2 float32 (m,), +inf there]."""
+        s = _f32(source, 3)
+        partner = np.empty(len(s), np.uint32)
+        d2 = np.empty(len(s), np.float32) if want_d2 else None
+        check(self._lib.pcpx_nearest_posed(self._h, _vp(s) if len(s) else None, len(s), _vp(self._pose16(pose)), float(radius), _vp(partner), _vp(d2)))
+        return (partner, d2) if want_d2 else partner
+
+    def nearest_posed_dev(self, d_source, m, radius, d_partner, d_pose=None, d_d2=None):
+        """Device form (torch tensors or device addresses: source float32 (m, 3), pose 16 float64 or None, partner uint32 (m,), d2
+        float32 (m,)), enqueued on the index's stream with no synchronisation."""
+        check(self._lib.pcpx_nearest_posed_dev(self._h, self._dptr(d_source), int(m), self._dptr(d_pose), float(radius), self._dptr(d_partner),
+                                               self._dptr(d_d2)))
+
+    def icp(self, source, radius, pose=None, max_iterations=50, normals=None, want_partner=False):
+        """Iterative closest point of `source` onto this cloud from `pose` (None: the identity): nearest partners within `radius`
+        under the pose, a new pose from the pairs, until the partner list repeats.  Point to point (Horn's least-squares fit over the
+        pairs, always of the original source) or, with `normals` ((n_in, 3) float32 by input row of this cloud), point to plane.
+        Returns a dict: "transform" ((4, 4) float64), "status" (0 = max_iterations reached, 1 = converged: the partners repeated,
+        2 = too few partners, 3 = degenerate normal equations), "iterations" (pose updates made), "last_count" (partners in the
+        last search), "count" and "rms" (per update, length iterations)[, "partner" uint32 (m,): the last partner list]."""
+        s = _f32(source, 3)
+        nrm = None
+        if normals is not None:
+            nrm = _f32(normals).reshape(-1)
+            if len(nrm) != 3 * self.n_in:
+                raise ValueError("one normal per input point")
+        it = int(max_iterations)
+        xf = np.empty(16, np.float64)
+        words = [C.c_uint32(0) for _ in range(3)]
+        count, rms = np.empty(max(it, 1), np.uint32), np.empty(max(it, 1), np.float64)
+        partner = np.empty(len(s), np.uint32) if want_partner else None
+        check(self._lib.pcpx_icp_rigid(self._h, _vp(s) if len(s) else None, len(s), _vp(self._pose16(pose)), float(radius), it,
+                                       _capi.PCPX_ICP_POINT_TO_PLANE if nrm is not None else 0, _vp(nrm), _vp(xf), *(C.byref(w) for w in words), _vp(count),
+                                       _vp(rms), _vp(partner)))
+        done = words[1].value
+        out = {"transform": xf.reshape(4, 4), "status": words[0].value, "iterations": done, "last_count": words[2].value,
+               "count": count[:done].copy(), "rms": rms[:done].copy()}
+        if want_partner:
+            out["partner"] = partner
+        return out
+
+    def icp_dev(self, d_source, m, radius, d_transform, d_pose=None, max_iterations=50, d_normals=None, d_status=None, d_iterations=None,
+                d_last_count=None, d_count=None, d_rms=None, d_partner=None):
+        """Device form: source float32 (m, 3); pose 16 float64 -- the refit array of ransac_rigid_dev goes straight in -- or None;
+        normals float32 (n_in, 3) for point to plane; transform 16 float64; status / iterations / last_count one uint32 each; count
+        uint32 and rms float64 with room for max_iterations; partner uint32 (m,).  All max_iterations rounds are enqueued on the
+        index's stream with no synchronisation and no read-back."""
+        check(self._lib.pcpx_icp_rigid_dev(self._h, self._dptr(d_source), int(m), self._dptr(d_pose), float(radius), int(max_iterations),
+                                           _capi.PCPX_ICP_POINT_TO_PLANE if d_normals is not None else 0,
+                                           *(self._dptr(d) for d in (d_normals, d_transform, d_status, d_iterations, d_last_count, d_count, d_rms,
+                                                                     d_partner))))
+
     # ---- normals ----
     def normals_knn_self(self, k, eps=1e-5, want_knn=False):
         nrm = np.empty((self.n_in, 3), np.float32)
@@ -649,7 +714,7 @@ class Index:
         return out
 
     def debug_set(self, name, value):
-        """pcpx_debug_set: 'long_groups_first', 'gather_outputs' (how work is done, never what comes out)."""
+        """pcpx_debug_set: 'long_groups_first', 'gather_outputs', 'icp_resort' (how work is done, never what comes out)."""
         check(self._lib.pcpx_debug_set(self._h, name.encode(), int(value)))
 
     def debug_get(self, name):

@@ -1,0 +1,288 @@
+"""CPU tests of iterative closest point (include/pcpx_icp.h): the companion header as C99, its symbols and
+bindings, the argument refusals (checked before the handle or any device is touched), the kernels' registers, the C++ programs of
+tests/cpp (icp_shape.cpp compiled only, the GPU tests run it; icp_refusals.cpp built and run), the one-thread point-to-plane solve of
+csrc/pcpx_plane_solve.h compiled for the host against numpy.linalg.solve, and the numpy model of the contract (tests/icp_model.py):
+its ties, the seeds of the recovery scene that the GPU tests rely on, the condition numbers of the plane steps."""
+import ctypes as C
+import importlib
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+import icp_model as M
+import register_model as RM
+
+F = np.float32
+NAMES = ["pcpx_icp_rigid", "pcpx_icp_rigid_dev", "pcpx_nearest_posed", "pcpx_nearest_posed_dev"]
+OTHER_TABLES = ("SIGNATURES", "RADIUS_SIGNATURES", "CLUSTER_SIGNATURES", "SUBSAMPLE_SIGNATURES", "SEGMENT_SIGNATURES", "FEATURES_SIGNATURES",
+                "KEYPOINTS_SIGNATURES", "DESCRIPTORS_SIGNATURES", "MATCH_SIGNATURES", "REGISTER_SIGNATURES")
+INVALID = -1
+
+
+@pytest.fixture(scope="module")
+def lib(pkg):
+    importlib.import_module("point-cloud-processing_amd.build").build()
+    return importlib.import_module("point-cloud-processing_amd._capi").load()
+
+
+def _declared():
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pcpx_icp.h")).read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(pcpx_[a-z0-9_]+)\s*\(", hdr)))
+
+
+def test_icp_header_compiles_as_c(tmp_path):
+    src = tmp_path / "t.c"
+    src.write_text('#include "pcpx_icp.h"\n'
+                   "int (*a)(pcpx_index*, const float*, uint64_t, const double*, float, uint32_t*, float*) = pcpx_nearest_posed_dev;\n"
+                   "int (*b)(pcpx_index*, const float*, uint64_t, const double*, float, uint32_t*, float*) = pcpx_nearest_posed;\n"
+                   "int (*c)(pcpx_index*, const float*, uint64_t, const double*, float, uint32_t, uint32_t, const float*, double*, uint32_t*, uint32_t*,"
+                   " uint32_t*, uint32_t*, double*, uint32_t*) = pcpx_icp_rigid_dev;\n"
+                   "int (*d)(pcpx_index*, const float*, uint64_t, const double*, float, uint32_t, uint32_t, const float*, double*, uint32_t*, uint32_t*,"
+                   " uint32_t*, uint32_t*, double*, uint32_t*) = pcpx_icp_rigid;\n"
+                   "int main(void){ return (a == 0) + (b == 0) + (c == 0) + (d == 0) + (PCPX_ICP_POINT_TO_PLANE != 1u) + (PCPX_ICP_NONE != 0xFFFFFFFFu)"
+                   " + (PCPX_ICP_EXHAUSTED != 0u) + (PCPX_ICP_CONVERGED != 1u) + (PCPX_ICP_STARVED != 2u) + (PCPX_ICP_DEGENERATE != 3u)"
+                   " + (PCPX_ICP_MAX_ITERATIONS != 1024u); }\n")
+    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o",
+                    str(tmp_path / "t.o")], check=True)
+
+
+def test_icp_symbols_exported_bound_and_disjoint(lib, pkg):
+    capi = importlib.import_module("point-cloud-processing_amd._capi")
+    declared = _declared()
+    assert declared == sorted(NAMES)
+    out = subprocess.run(["nm", "-D", "--defined-only", capi.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = set(re.findall(r" T (pcpx_[a-z0-9_]+)", out))
+    assert sorted(s for s in exported if s.startswith(("pcpx_icp", "pcpx_nearest"))) == declared
+    assert sorted(capi.ICP_SIGNATURES) == declared
+    for table in OTHER_TABLES:
+        assert not set(capi.ICP_SIGNATURES) & set(getattr(capi, table)), table
+    for name in declared:
+        assert getattr(lib, name).argtypes == capi.ICP_SIGNATURES[name][1]
+        assert getattr(lib, name).restype == capi.ICP_SIGNATURES[name][0]
+    # the host and the _dev form take the same arguments; the C header's parameter counts are the tables'
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pcpx_icp.h")).read(), flags=re.S)
+    for name in declared:
+        params = re.search(r"\b%s\s*\(([^)]*)\)" % name, hdr).group(1)
+        assert len(params.split(",")) == len(capi.ICP_SIGNATURES[name][1]), name
+    assert capi.ABI_VERSION == 5 and lib.pcpx_abi_version() == 5  # pcpx.h and its ABI version stay what they were
+    assert (capi.PCPX_ICP_NONE, capi.PCPX_ICP_POINT_TO_PLANE, capi.PCPX_ICP_MAX_ITERATIONS) == (0xFFFFFFFF, 1, 1024)
+    assert (capi.PCPX_ICP_EXHAUSTED, capi.PCPX_ICP_CONVERGED, capi.PCPX_ICP_STARVED, capi.PCPX_ICP_DEGENERATE) == (M.EXHAUSTED, M.CONVERGED, M.STARVED,
+                                                                                                                  M.DEGENERATE)
+    for fn in ("nearest_posed", "nearest_posed_dev", "icp", "icp_dev"):
+        assert callable(getattr(pkg.Index, fn))
+
+
+# ---- refusals: PCPX_ERR_INVALID from the arguments alone (a NULL handle is passed: the checks come before it) -----------------------------
+def _call(lib, name, s=1, m=8, radius=0.5, it=10, flags=0, normals=0, out=1, partner=1):
+    a = np.zeros(64, F)
+    x = np.full(16, 7.0)
+    pr = np.full(8, 9, np.uint32)
+    ptr = lambda on, arr: arr.ctypes.data_as(C.c_void_p) if on else None
+    if "nearest" in name:
+        st = getattr(lib, name)(None, ptr(s, a), m, None, radius, ptr(partner, pr), None)
+    else:
+        st = getattr(lib, name)(None, ptr(s, a), m, None, radius, it, flags, ptr(normals, a), ptr(out, x), None, None, None, None, None, ptr(partner, pr))
+    assert x.tolist() == [7.0] * 16 and pr.tolist() == [9] * 8  # (a refused call writes nothing)
+    return st
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_icp_argument_refusals(lib, name):
+    for radius in (-1e-30, -1.0, float("nan"), float("inf"), float("-inf")):
+        assert _call(lib, name, radius=radius) == INVALID, radius
+        assert b"radius" in lib.pcpx_last_error()
+    for m in (0xFFFFFFFF, 2 ** 32, 2 ** 40):
+        assert _call(lib, name, m=m) == INVALID, m
+        assert b"source points" in lib.pcpx_last_error()
+    assert _call(lib, name, s=0) == INVALID and b"source array" in lib.pcpx_last_error()
+    if "nearest" in name:
+        assert _call(lib, name, partner=0) == INVALID and b"partner" in lib.pcpx_last_error()
+    else:
+        for it in (0, 1025, 0xFFFFFFFF):
+            assert _call(lib, name, it=it) == INVALID and b"max_iterations" in lib.pcpx_last_error(), it
+        for flags in (2, 0x80000001, 0x80000000):
+            assert _call(lib, name, flags=flags) == INVALID and b"flag" in lib.pcpx_last_error(), flags
+        assert _call(lib, name, flags=1) == INVALID and b"without normals" in lib.pcpx_last_error()
+        assert _call(lib, name, normals=1) == INVALID and b"normals without" in lib.pcpx_last_error()
+        assert _call(lib, name, out=0) == INVALID and b"transform" in lib.pcpx_last_error()
+    # good arguments, and an empty source, get as far as the handle
+    assert _call(lib, name) == INVALID and b"null handle" in lib.pcpx_last_error()
+    assert _call(lib, name, s=0, m=0) == INVALID and b"null handle" in lib.pcpx_last_error()
+
+
+@pytest.mark.timeout(600)
+def test_icp_kernels_use_no_scratch_and_spill_nothing():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), "pcpx_icp.hip", "k_"],
+                         capture_output=True, text=True, timeout=580, check=True).stdout
+    rows = dict((m[0], [int(v) for v in m[1:]]) for m in re.findall(
+        r"(k_\w+(?:<[^>]*>)?)\(.*?vgpr\s+(\d+) sgpr\s+(\d+) sspill\s+(\d+) vspill\s+(\d+) scratch\s+(\d+) lds\s+(\d+)", out))
+    assert len(out.strip().splitlines()) == len(rows), out  # (every kernel of the file is among them)
+    assert sorted(rows) == ["k_icp_commit", "k_icp_decide", "k_icp_finish", "k_icp_init", "k_icp_moved", "k_nearest_posed", "k_plane_final",
+                            "k_plane_partial", "k_plane_solve"], out
+    for name, (vgpr, sgpr, sspill, vspill, scratch, lds) in rows.items():
+        assert scratch == 0 and vspill == 0 and sspill == 0, (name, out)
+        assert lds == 0 or name == "k_plane_partial", (name, out)  # (the plane sums' block tree)
+        assert vgpr <= 128 and sgpr <= 102, (name, out)
+    assert rows["k_nearest_posed"][5] == 0 and rows["k_nearest_posed"][0] <= 64, out  # no LDS, and eight waves a SIMD by its vector registers
+
+
+def test_cpp_icp_program_compiles(tmp_path, pkg):
+    inc = os.path.join(ROOT, "include")
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I", inc, "-c", os.path.join(ROOT, "tests", "cpp", "icp_shape.cpp"),
+                    "-o", str(tmp_path / "icp_shape.o")], check=True)
+
+
+def test_cpp_icp_refusals_program_runs_without_a_device(tmp_path, lib):
+    capi = importlib.import_module("point-cloud-processing_amd._capi")
+    inc, pkgdir = os.path.join(ROOT, "include"), os.path.dirname(capi.LIB_PATH)
+    exe = str(tmp_path / "icp_refusals")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", inc, os.path.join(ROOT, "tests", "cpp", "icp_refusals.cpp"),
+                    "-o", exe, "-L", pkgdir, "-lpcpx", "-Wl,-rpath," + pkgdir, "-Wl,-rpath-link,/opt/rocm/lib", "-pthread"], check=True)
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0 and "0 checks failed" in res.stdout, res.stdout[-2000:] + res.stderr[-2000:]
+
+
+# ---- the one-thread solve, compiled for the host ------------------------------------------------------------------------------------------
+def test_plane_solve_on_the_host_equals_numpy(tmp_path):
+    src = tmp_path / "solve.cpp"
+    src.write_text('#include "pcpx_plane_solve.h"\n#include <cstdio>\n'
+                   "int main()\n{\n    double v[46];\n    for (;;) {\n"
+                   "        for (int i = 0; i < 46; ++i) {\n            if (std::scanf(\"%la\", v + i) != 1) return 0;\n        }\n"
+                   "        double a[21], b[6], x[6] = {0, 0, 0, 0, 0, 0}, o[3], out[16];\n"
+                   "        for (int i = 0; i < 21; ++i) a[i] = v[i];\n"
+                   "        for (int i = 0; i < 6; ++i) b[i] = v[21 + i];\n"
+                   "        for (int i = 0; i < 3; ++i) o[i] = v[43 + i];\n"
+                   "        const bool ok = pcpx::plane_cholesky(a, b, x);\n"
+                   "        pcpx::plane_compose(v + 27, o, x, out);\n"
+                   "        std::printf(\"%d\", ok ? 1 : 0);\n"
+                   "        for (int i = 0; i < 6; ++i) std::printf(\" %a\", x[i]);\n"
+                   "        for (int i = 0; i < 16; ++i) std::printf(\" %a\", out[i]);\n"
+                   "        std::printf(\"\\n\");\n    }\n}\n")
+    exe = str(tmp_path / "solve")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-Wno-unknown-pragmas", "-I",
+                    os.path.join(ROOT, "point-cloud-processing_amd", "csrc"), str(src), "-o", exe], check=True)
+    rng = np.random.default_rng(4)
+    iu = np.triu_indices(6)
+    cases = []
+    for i in range(40):
+        J = rng.normal(size=(50, 6)) * rng.uniform(0.1, 10, 6)
+        A, b = J.T @ J, rng.normal(size=6)
+        T = M.rigid(rng.normal(size=3), rng.uniform(0, 180), rng.normal(size=3))
+        cases.append((A, b, T, rng.normal(size=3) * 10))
+    flat = np.diag([1.0, 2.0, 0.0, 0.0, 0.0, 3.0])                     # exact zero pivots
+    cases.append((flat, np.ones(6), np.eye(4), np.zeros(3)))
+    thin = np.eye(6)
+    thin[4, 5] = thin[5, 4] = np.sqrt(1.0 - 2.0 ** -41)                 # the last pivot is about 2^-41 of its own diagonal entry: refused
+    cases.append((thin, np.ones(6), np.eye(4), np.zeros(3)))
+    cases.append((np.diag([1.0, 1.0, np.nan, 1.0, 1.0, 1.0]), np.ones(6), np.eye(4), np.zeros(3)))
+    cases.append((np.diag([1.0, 1.0, np.inf, 1.0, 1.0, 1.0]), np.ones(6), np.eye(4), np.zeros(3)))
+    text = "\n".join(" ".join(float(v).hex() for v in np.concatenate([A[iu], b, T.reshape(16), o])) for A, b, T, o in cases) + "\n"
+    out = subprocess.run([exe], input=text, capture_output=True, text=True, check=True, timeout=60).stdout.strip().split("\n")
+    assert len(out) == len(cases)
+    for i, (A, b, T, o) in enumerate(cases):
+        words = out[i].split()
+        ok, vals = int(words[0]), np.array([float.fromhex(v) for v in words[1:]])
+        assert ok == (1 if i < 40 else 0), i
+        assert (M.cholesky_solve(A, b) is not None) == bool(ok), i  # the model's pivot rule is the header's
+        if not ok:
+            continue
+        x, got = vals[:6], vals[6:].reshape(4, 4)
+        want = np.linalg.solve(A, b)
+        assert np.abs(x - want).max() <= 1e-12 * np.linalg.cond(A) * np.abs(want).max(), i
+        R = got[:3, :3]
+        dR = R @ T[:3, :3].T
+        assert np.abs(dR.T @ dR - np.eye(3)).max() <= 1e-14 and abs(np.linalg.det(dR) - 1) <= 1e-14, i  # always a proper rotation
+        assert np.abs(got - M.plane_compose(T, o, x)).max() <= 1e-12 * max(1.0, np.abs(got).max()), i
+        assert got[3].tolist() == [0, 0, 0, 1]
+    # the Cayley step equals the exponential to second order
+    for w in (np.array([1e-3, -2e-3, 5e-4]), np.array([0.02, 0.01, -0.03])):
+        assert np.abs(M.cayley(w) - M.rotation(w, np.rad2deg(np.linalg.norm(w)))).max() <= np.linalg.norm(w) ** 3
+
+
+# ---- the model ----------------------------------------------------------------------------------------------------------------------------
+def test_model_moved_point_is_the_written_formula():
+    s = np.array([[0.1, 0.2, 0.3], [1e8, -3.0, 7.0]], F)
+    T = M.rigid([1, 2, 3], 33.0, [0.5, -2.0, 1e-3])
+    y = M.moved64(s, T)
+    for i in range(2):
+        a, b, c = (float(v) for v in s[i])
+        for r in range(3):
+            assert y[i, r] == ((T[r, 0] * a + T[r, 1] * b) + T[r, 2] * c) + T[r, 3]
+    assert np.array_equal(M.moved32(s, None), s) and M.moved32(s, T).dtype == F
+    bad = M.moved32(np.array([[np.inf, 0, 0], [np.nan, 1, 1]], F), None)  # NULL is evaluated as the identity matrix: 0 * inf
+    assert np.isnan(bad).any(1).all()
+
+
+def test_model_ties_go_to_the_lowest_index_and_the_bound_is_inclusive():
+    g = np.arange(3, dtype=F)
+    grid = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
+    s = np.array([[0.5, 0.5, 0.5], [0.5, 0.5, 0], [0.5, 0, 0], [1.5, 1.5, 1.5]], F)
+    partner, d2 = M.nearest_posed(grid, s, None, 1.0)
+    assert partner.tolist() == [0, 0, 0, 13] and d2.tolist() == [0.75, 0.5, 0.25, 0.75]
+    back = grid[::-1].copy()  # reversed rows: the winner is another point, still the lowest index
+    assert M.nearest_posed(back, s, None, 1.0)[0].tolist() == [26 - 13, 26 - 12, 26 - 9, 26 - 26]
+    # d2 == radius^2 is inside, just below is not; no partner: NONE and +inf
+    assert M.nearest_posed(grid, s[2:3], None, 0.5)[0].tolist() == [0]
+    partner, d2 = M.nearest_posed(grid, s[2:3], None, float(np.nextafter(F(0.5), F(0))))
+    assert partner.tolist() == [M.NONE] and np.isinf(d2).all()
+    # rows that are not indexed are never partners; an empty target; non-finite rows
+    inside = np.ones(27, bool)
+    inside[0] = False
+    assert M.nearest_posed(grid, s[:3], None, 1.0, indexed=inside)[0].tolist() == [1, 3, 9]
+    assert M.nearest_posed(np.zeros((0, 3), F), s, None, 1.0)[0].tolist() == [M.NONE] * 4
+    assert M.nearest_posed(grid, np.array([[np.nan, 0, 0], [0, np.inf, 0]], F), None, 100.0)[0].tolist() == [M.NONE] * 2
+
+
+def _model_fit(p, q, pairs):
+    return RM.rigid_fit(p, q, pairs)
+
+
+def test_model_recovery_scene_converges_with_every_partner_the_true_one():
+    target, normals, rows, source, truth, extent = M.recovery_scene()
+    assert len(target) == 2000 and len(source) == 500
+    moved = np.linalg.norm(M.moved64(source, None) - target[rows], axis=1)
+    assert 0.04 * extent <= moved.max() <= 0.2 * extent  # a 5 degree turn and 0.05 of the extent
+    run = M.icp_point_to_point(target, source, None, M.RECOVERY_RADIUS, M.RECOVERY_ITERATIONS, _model_fit)
+    assert run.status == M.CONVERGED and 1 < run.iterations < M.RECOVERY_ITERATIONS
+    assert np.array_equal(run.partner, rows.astype(np.uint32))
+    assert M.corner_error(run.transform, truth, target) / extent <= 1e-6
+    assert (run.count[:run.iterations] == 500).all() and run.count[run.iterations:].tolist() == [0] * (M.RECOVERY_ITERATIONS - run.iterations)
+    assert np.isnan(run.rms[run.iterations:]).all() and (np.diff(run.rms[:run.iterations]) <= 0).all()  # the rms never grows
+    # point to plane: fewer steps, every system well conditioned
+    conditions = []
+    bbox = np.concatenate([target.min(0), target.max(0)])
+    plane = M.icp_point_to_plane(target, normals, source, None, M.RECOVERY_RADIUS, M.RECOVERY_ITERATIONS, bbox, conditions=conditions)
+    assert plane.status == M.CONVERGED and np.array_equal(plane.partner, rows.astype(np.uint32))
+    assert len(conditions) == plane.iterations and max(conditions) <= 1e4
+    assert plane.iterations <= run.iterations
+    assert M.corner_error(plane.transform, truth, target) / extent <= 1e-6
+    for T in plane.poses:
+        assert np.abs(T[:3, :3].T @ T[:3, :3] - np.eye(3)).max() <= 1e-12 and abs(np.linalg.det(T[:3, :3]) - 1) <= 1e-12
+
+
+def test_model_stopping_rules():
+    target, normals, rows, source, truth, extent = M.recovery_scene()
+    one = M.icp_point_to_point(target, source, None, M.RECOVERY_RADIUS, 1, _model_fit)
+    assert (one.status, one.iterations) == (M.EXHAUSTED, 1) and len(one.poses) == 2
+    starved = M.icp_point_to_point(target, source, None, 0.0, 5, _model_fit)
+    assert (starved.status, starved.iterations, starved.last_count) == (M.STARVED, 0, 0) and np.array_equal(starved.transform, np.eye(4).reshape(16))
+    nan = M.icp_point_to_point(target, np.full((70, 3), np.nan, F), truth, 10.0, 5, _model_fit)
+    assert (nan.status, nan.last_count) == (M.STARVED, 0) and np.array_equal(nan.transform, truth.reshape(16))
+    bbox = np.concatenate([target.min(0), target.max(0)])
+    few = M.icp_point_to_plane(target, normals, source[:5], None, M.RECOVERY_RADIUS, 5, bbox)
+    assert (few.status, few.last_count) == (M.STARVED, 5)
+    # a flat target: three columns of J are exactly zero
+    g = np.arange(20, dtype=F) / F(16)
+    flat = np.stack(list(np.meshgrid(g, g, indexing="ij")) + [np.zeros((20, 20), F)], -1).reshape(-1, 3).astype(F)
+    up = np.tile(np.array([0, 0, 1], F), (len(flat), 1))
+    src = (flat[::3] + np.array([0.01, -0.01, 0.02], F)).astype(F)
+    box = np.concatenate([flat.min(0), flat.max(0)])
+    partner, _ = M.nearest_posed(flat, src, None, 0.2)
+    A, _b, _ss, n = M.plane_system(flat, up, src, np.eye(4), partner, M.box_centre(box))
+    assert n >= 6 and not A[2].any() and not A[3].any() and not A[4].any()
+    assert M.icp_point_to_plane(flat, up, src, None, 0.2, 10, box).status == M.DEGENERATE
