@@ -46,6 +46,13 @@ class HierarchyParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("cluster_size", C.c_uint64), ("var_max", C.c_double)]
 
 
+class PlaneParams(C.Structure):
+    """pcpx_plane_params (include/pcpx_planes.h)."""
+    _fields_ = [("hypotheses", C.c_uint64), ("seed", C.c_uint32), ("flags", C.c_uint32), ("max_distance", C.c_float),
+                ("min_normal_cos", C.c_float), ("axis", C.c_float * 3), ("min_axis_cos", C.c_float), ("origin_row", C.c_uint32),
+                ("min_inliers", C.c_uint32), ("max_planes", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 K_BUILD, K_KNN, K_NORMALS, K_RANGE, K_QUERY_PREP = range(5)
 
 
@@ -304,6 +311,28 @@ ICP_SIGNATURES = {
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/pcpx_planes.h (plane detection)
+PCPX_PLANE_REFIT = 1
+PCPX_PLANE_NORMALS = 2
+PCPX_PLANE_AXIS = 4
+PCPX_PLANE_NONE = 0xFFFFFFFF
+PCPX_PLANE_ORIGIN_FIRST = 0xFFFFFFFF
+PCPX_PLANES_MAX = 64
+_ppp = C.POINTER(PlaneParams)
+PLANES_SIGNATURES = {
+    "pcpx_plane_plan": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, u32p, u64p, u64p]),
+    "pcpx_plane_ransac_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, _ppp, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcpx_plane_ransac": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, _ppp, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcpx_plane_fit_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcpx_plane_fit": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]),
+    "pcpx_extract_planes_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, _ppp, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    "pcpx_extract_planes": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, _ppp, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+}
+
 
 def load():
     """Load libpcpx.so; raises if it has not been built (run __graft_entry__.build())."""
@@ -319,7 +348,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(RADIUS_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items())\
             + list(SUBSAMPLE_SIGNATURES.items()) + list(SEGMENT_SIGNATURES.items()) + list(FEATURES_SIGNATURES.items())\
             + list(KEYPOINTS_SIGNATURES.items()) + list(DESCRIPTORS_SIGNATURES.items()) + list(MATCH_SIGNATURES.items())\
-            + list(REGISTER_SIGNATURES.items()) + list(ICP_SIGNATURES.items()):
+            + list(REGISTER_SIGNATURES.items()) + list(ICP_SIGNATURES.items()) + list(PLANES_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

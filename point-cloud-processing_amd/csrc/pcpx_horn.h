@@ -18,9 +18,10 @@ namespace pcpx {
 
 constexpr int HORN_MAX_SWEEPS = 64;  // (convergence is quadratic: a dozen sweeps at the most in practice)
 
-// one Jacobi rotation in the plane (P, Q) of the symmetric a, accumulated into the eigenvector columns of v
-template <int P, int Q>
-PCPX_HORN_FN void horn_rotate(double (&a)[4][4], double (&v)[4][4])
+// one Jacobi rotation in the plane (P, Q) of the symmetric N x N a, accumulated into the eigenvector columns of v (N = 4: Horn's
+// matrix below; N = 3: the scatter matrix of pcpx_plane_fit.h)
+template <int N, int P, int Q>
+PCPX_HORN_FN void jacobi_rotate(double (&a)[N][N], double (&v)[N][N])
 {
     const double apq = a[P][Q];
     if (apq == 0.0) return;
@@ -33,7 +34,7 @@ PCPX_HORN_FN void horn_rotate(double (&a)[4][4], double (&v)[4][4])
     const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
     const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {  // a <- a J, v <- v J with J[P][P] = J[Q][Q] = c, J[P][Q] = s, J[Q][P] = -s
+    for (int k = 0; k < N; ++k) {  // a <- a J, v <- v J with J[P][P] = J[Q][Q] = c, J[P][Q] = s, J[Q][P] = -s
         const double akp = a[k][P], akq = a[k][Q];
         a[k][P] = c * akp - s * akq;
         a[k][Q] = s * akp + c * akq;
@@ -42,12 +43,17 @@ PCPX_HORN_FN void horn_rotate(double (&a)[4][4], double (&v)[4][4])
         v[k][Q] = s * vkp + c * vkq;
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {  // a <- J^T a
+    for (int k = 0; k < N; ++k) {  // a <- J^T a
         const double apk = a[P][k], aqk = a[Q][k];
         a[P][k] = c * apk - s * aqk;
         a[Q][k] = s * apk + c * aqk;
     }
     a[P][Q] = a[Q][P] = 0.0;
+}
+template <int P, int Q>
+PCPX_HORN_FN void horn_rotate(double (&a)[4][4], double (&v)[4][4])
+{
+    jacobi_rotate<4, P, Q>(a, v);
 }
 
 // the rotation matrix, row-major, of the unit quaternion (qw, qx, qy, qz)

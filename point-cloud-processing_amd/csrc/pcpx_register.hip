@@ -11,6 +11,7 @@
 #include "pcpx_device.h"
 #include "pcpx_horn.h"
 #include "pcpx_lease.h"
+#include "pcpx_ransac.h"
 #include "pcpx_register.h"
 #include "pcpx_scan.h"
 
@@ -21,11 +22,8 @@ namespace pcpx {
 
 namespace {
 
-constexpr u32 RG_BLOCK = 256;  // threads of the row-wise kernels
 constexpr u32 RG_WAVES = 4;    // waves of a k_ransac_count block: four consecutive hypothesis groups on one segment (they share its records in the scalar cache)
 constexpr u32 RG_UNROLL = 4;   // records of one trip of k_ransac_count's loop
-constexpr u32 RG_BEST_PER_THREAD = 16;  // hypotheses of a k_ransac_best thread
-constexpr u32 RG_INVALID = 0xFFFFFFFFu;  // the count word of an invalid hypothesis (a count is at most C < 2^32 - 1)
 // The plan, by the reasoning of pcpx_match.hip's: a wave is 64 hypotheses on one segment, a call should be several rounds of what
 // the device holds, a segment is never shorter than RG_MIN_SEGMENT_ROWS (a wave's prologue -- three gathers and the two frames --
 // is paid per segment) and there are never more than RG_MAX_SEGMENTS (k_ransac_best reads a word per hypothesis and segment).
@@ -33,15 +31,10 @@ constexpr u64 RG_TARGET_WAVES = 16384;
 constexpr u64 RG_MAX_SEGMENTS = 256;
 constexpr u64 RG_MIN_SEGMENT_ROWS = 256;
 constexpr u64 RG_LAUNCH_HYPOTHESES = 1ull << 30;  // hypotheses of one launch (a grid's thread count stays below 2^32)
-// the fit: FIT_BLOCKS blocks of RG_BLOCK threads stride over the pairs; a block leaves FIT_TERMS doubles
-constexpr u32 FIT_BLOCKS = 64;
-constexpr u32 FIT_TERMS = 16;
 // the doubles of the fit's state: [0] the number of usable pairs, [1..3] sum p, [4..6] sum q, [8..10] pbar, [11..13] qbar,
 // [16..24] H, [32] sum of squared residuals, [40..55] the transform
 constexpr u32 FIT_STATE = 64, FS_N = 0, FS_SUM = 1, FS_PBAR = 8, FS_QBAR = 11, FS_H = 16, FS_SS = 32, FS_XF = 40;
 
-inline u32 blocks_of(u64 n, u32 per) { return static_cast<u32>((n + per - 1) / per); }
-inline size_t padded(u64 bytes) { return (bytes + 255) / 256 * 256; }
 
 struct Rec {
     float v[8];  // p - o_p, q - o_q, 0, 0
@@ -271,32 +264,7 @@ __global__ __launch_bounds__(64 * RG_WAVES) void k_ransac_count(const Rec* __res
     if (active) counts[static_cast<u64>(blockIdx.y) * T + h] = valid ? n : RG_INVALID;
 }
 
-// RG_BEST_PER_THREAD hypotheses per thread, a block's threads side by side in each round: the sum of a hypothesis's segment counts
-// (integers: exact, and independent of the split), the key ((count + 1) << 32 | (0xFFFFFFFF - h)) of a valid one -- larger count
-// first, then lower h -- and 0 of an invalid one; the largest key of the wave goes to *key by one atomicMax, and only where it is
-// above what *key already holds (62 500 atomics on the one word were a quarter of a call of 4 000 000 hypotheses: DESIGN.md
-// section 24).  The maximum does not depend on the order; a stale read of *key only costs an atomic.
-__global__ __launch_bounds__(RG_BLOCK) void k_ransac_best(const u32* __restrict__ counts, u64 h_base, u64 h_end, u64 T, u32 segments, u64* __restrict__ key)
-{
-    u64 k = 0;
-#pragma unroll 4
-    for (u32 j = 0; j < RG_BEST_PER_THREAD; ++j) {
-        const u64 h = h_base + (static_cast<u64>(blockIdx.x) * RG_BEST_PER_THREAD + j) * RG_BLOCK + threadIdx.x;
-        if (h >= h_end) break;
-        u32 sum = counts[h];
-        if (sum == RG_INVALID) continue;
-        for (u32 s = 1; s < segments; ++s) sum += counts[static_cast<u64>(s) * T + h];
-        const u64 mine = (static_cast<u64>(sum + 1u) << 32) | (0xFFFFFFFFu - static_cast<u32>(h));
-        k = mine > k ? mine : k;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const u64 other = __shfl_xor(k, off);
-        k = other > k ? other : k;
-    }
-    if ((threadIdx.x & 63u) == 0 && k > __hip_atomic_load(key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-        atomicMax(reinterpret_cast<unsigned long long*>(key), static_cast<unsigned long long>(k));
-}
+// (k_ransac_best, the best-key reduction over the counts: pcpx_ransac.h)
 
 __device__ __forceinline__ void store_identity(double* xf)
 {
@@ -339,17 +307,7 @@ __global__ __launch_bounds__(RG_BLOCK) void k_ransac_emit(Pairs in, const Rec* _
     xf[15] = 1.0;
 }
 
-struct IsFlagged {
-    const uint8_t* flag;
-    __device__ u32 operator()(u32 i) const { return flag[i]; }
-};
-
-__global__ __launch_bounds__(RG_BLOCK) void k_reg_compact(u32 capacity, const uint8_t* __restrict__ flag, const u32* __restrict__ place,
-                                                         u32* __restrict__ positions)
-{
-    const u32 k = blockIdx.x * RG_BLOCK + threadIdx.x;
-    if (k < capacity && flag[k]) positions[place[k]] = k;
-}
+// (IsFlagged and k_reg_compact: pcpx_ransac.h)
 
 // ---- the rigid fit ---------------------------------------------------------------------------------------------------------------------
 // the pairs of a fit: all correspondences, or those at the listed positions
@@ -386,7 +344,6 @@ template <int PASS>
 __global__ __launch_bounds__(RG_BLOCK) void k_fit_partial(FitSet set, const double* __restrict__ state, double* __restrict__ partial)
 {
     constexpr int NT = fit_terms(PASS);
-    __shared__ double tree[RG_BLOCK];
     const u32 C = set.in.count(), n = set.items(C);
     double acc[NT];
 #pragma unroll
@@ -413,17 +370,7 @@ __global__ __launch_bounds__(RG_BLOCK) void k_fit_partial(FitSet set, const doub
             }
         }
     }
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
-        tree[threadIdx.x] = acc[i];
-        __syncthreads();
-        for (u32 off = RG_BLOCK / 2; off > 0; off >>= 1) {
-            if (threadIdx.x < off) tree[threadIdx.x] += tree[threadIdx.x + off];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) partial[blockIdx.x * FIT_TERMS + i] = tree[0];
-        __syncthreads();
-    }
+    fit_block_sums<NT>(acc, partial);  // (pcpx_ransac.h: the fixed tree)
 }
 
 // One block: thread `term` adds the blocks' partial sums of its term in block order.  Pass 1 also leaves the centroids; pass 3 the
@@ -433,9 +380,7 @@ __global__ __launch_bounds__(64) void k_fit_final(const double* __restrict__ par
 {
     constexpr int NT = fit_terms(PASS);
     if (threadIdx.x >= NT) return;
-    double sum = 0.0;
-#pragma unroll 16
-    for (u32 b = 0; b < nblocks; ++b) sum += partial[b * FIT_TERMS + threadIdx.x];  // (in block order; the loads of a batch are issued together)
+    const double sum = fit_sum_blocks(partial, nblocks, threadIdx.x);  // (pcpx_ransac.h: in block order)
     if constexpr (PASS == 1) {
         const double n = __shfl(sum, 0);
         state[FS_N + threadIdx.x] = sum;  // (FS_SUM = FS_N + 1)
