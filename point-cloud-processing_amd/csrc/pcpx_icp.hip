@@ -5,9 +5,11 @@
 //   k_icp_moved       the source under a pose, rounded to float32: what the curve sort of pcpx_prep.hip orders, once per call
 //   k_nearest_posed   one wavefront per 64 consecutive positions of that order, one lane per source point
 //   k_icp_init / k_icp_decide / k_icp_commit / k_icp_finish   the loop's rules on a block of device words, a thread or a wave each
-//   k_plane_partial / k_plane_final / k_plane_solve   the point-to-plane step: 29 float64 sums in the fit's fixed order, Cholesky
+//   k_fixed_partial / k_fixed_final (pcpx_fixed_sum.h) over PlaneSystem, k_plane_solve   the point-to-plane step: 29 float64 sums in
+//                     the fits' fixed order, Cholesky
 // The point-to-point step is the rigid fit of pcpx_register.hip through fit_pairs_device: the same kernels, so the same bits.
 #include "pcpx_device.h"
+#include "pcpx_fixed_sum.h"
 #include "pcpx_icp.h"
 #include "pcpx_lease.h"
 #include "pcpx_plane_solve.h"
@@ -31,11 +33,9 @@ constexpr bool ICP_PREVIOUS_START = true;
 // k_nearest_posed's two counts of a round are spread over ICP_SLOTS words ICP_SLOT_STRIDE words apart, wave g adding to slot
 // g mod ICP_SLOTS: 15 625 atomics of a million-point source on ONE word took twice as long as the search itself.
 constexpr u32 ICP_SLOTS = 64, ICP_SLOT_STRIDE = 32;
-constexpr u32 PLANE_BLOCKS = 64;  // the grid of the plane sums: fixed, so their order depends on the pairs alone
 constexpr u32 PLANE_TERMS = PLANE_A_TERMS + PLANE_B_TERMS + 2, PLANE_STRIDE = 32;  // A, b, sum rho^2, rows
 
 inline u32 blocks_of(u64 n, u32 per) { return static_cast<u32>((n + per - 1) / per); }
-inline size_t padded(u64 bytes) { return (bytes + 255) / 256 * 256; }
 
 // The words of a loop on the device.  done: every kernel of a later round reads it first and returns.  fit_count: the number of
 // correspondences the fit's kernels see -- m while the loop runs, 0 once it has stopped, so that they pass over nothing and stay
@@ -252,25 +252,28 @@ struct PlaneIn {
     double o[3];
 };
 
-// PLANE_BLOCKS blocks of ICP_BLOCK threads stride over the rows; a thread adds its rows in ascending order, the block's threads are
-// added by a fixed tree, and the block leaves its sums in partial[block * PLANE_STRIDE + term] (as k_fit_partial, pcpx_register.hip).
-__global__ __launch_bounds__(ICP_BLOCK) void k_plane_partial(PlaneIn in, const IcpState* __restrict__ st, double* __restrict__ partial)
-{
-    __shared__ double tree[ICP_BLOCK];
-    const u32 m = st->done ? 0u : in.m;
-    Pose12 T;
+// The sums of the normal equations over the rows that have a partner, in pcpx_fixed_sum.h's order; the totals go to st->plane.  Once
+// the loop has stopped there are no rows: the launches still run, and leave zeros.
+struct PlaneSystem {
+    static constexpr int TERMS = PLANE_TERMS, STRIDE = PLANE_STRIDE;
+    PlaneIn in;
+    IcpState* st;
+    Pose12 T;  // (items() leaves the round's pose here for add())
+    __device__ __forceinline__ bool live() const { return true; }
+    __device__ __forceinline__ u32 items()
+    {
 #pragma unroll
-    for (int j = 0; j < 12; ++j) T.v[j] = st->pose[j];
-    double acc[PLANE_TERMS];
-#pragma unroll
-    for (u32 i = 0; i < PLANE_TERMS; ++i) acc[i] = 0.0;
-    for (u64 j = static_cast<u64>(blockIdx.x) * ICP_BLOCK + threadIdx.x; j < m; j += static_cast<u64>(gridDim.x) * ICP_BLOCK) {
+        for (int j = 0; j < 12; ++j) T.v[j] = st->pose[j];
+        return st->done ? 0u : in.m;
+    }
+    __device__ __forceinline__ void add(u32 j, double (&acc)[TERMS]) const
+    {
         const u32 target = in.pairs[j].y;
-        if (target >= in.n_in) continue;  // (no partner)
+        if (target >= in.n_in) return;  // (no partner)
         const float n0 = in.normals[3ull * target], n1 = in.normals[3ull * target + 1], n2 = in.normals[3ull * target + 2];
-        if (!(std::isfinite(n0) && std::isfinite(n1) && std::isfinite(n2))) continue;
+        if (!(std::isfinite(n0) && std::isfinite(n1) && std::isfinite(n2))) return;
         double y[3];
-        moved_point(T, in.s[3 * j], in.s[3 * j + 1], in.s[3 * j + 2], y);
+        moved_point(T, in.s[3ull * j], in.s[3ull * j + 1], in.s[3ull * j + 2], y);
         const double e0 = y[0] - static_cast<double>(in.xyz[3ull * target]), e1 = y[1] - static_cast<double>(in.xyz[3ull * target + 1]),
                      e2 = y[2] - static_cast<double>(in.xyz[3ull * target + 2]);
         const double u0 = y[0] - in.o[0], u1 = y[1] - in.o[1], u2 = y[2] - in.o[2];
@@ -289,28 +292,8 @@ __global__ __launch_bounds__(ICP_BLOCK) void k_plane_partial(PlaneIn in, const I
         acc[PLANE_A_TERMS + PLANE_B_TERMS] += rho * rho;
         acc[PLANE_A_TERMS + PLANE_B_TERMS + 1] += 1.0;
     }
-#pragma unroll
-    for (u32 i = 0; i < PLANE_TERMS; ++i) {
-        tree[threadIdx.x] = acc[i];
-        __syncthreads();
-        for (u32 off = ICP_BLOCK / 2; off > 0; off >>= 1) {
-            if (threadIdx.x < off) tree[threadIdx.x] += tree[threadIdx.x + off];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) partial[blockIdx.x * PLANE_STRIDE + i] = tree[0];
-        __syncthreads();
-    }
-}
-
-// thread `term` adds the blocks' partial sums of its term in block order
-__global__ __launch_bounds__(64) void k_plane_final(const double* __restrict__ partial, IcpState* __restrict__ st)
-{
-    if (threadIdx.x >= PLANE_TERMS) return;
-    double sum = 0.0;
-#pragma unroll 16
-    for (u32 b = 0; b < PLANE_BLOCKS; ++b) sum += partial[b * PLANE_STRIDE + threadIdx.x];
-    st->plane[threadIdx.x] = sum;
-}
+    __device__ __forceinline__ void finish(u32 term, double sum) const { st->plane[term] = sum; }
+};
 
 // one thread: Cholesky, the Cayley step and the new pose into cand, or the degenerate word
 __global__ __launch_bounds__(64) void k_plane_solve(IcpState* __restrict__ st, double o0, double o1, double o2)
@@ -396,22 +379,17 @@ struct IcpScratch {
     size_t state = 0, y32 = 0, order = 0, pairs0 = 0, pairs1 = 0, fit = 0, plane = 0, bytes = 0;
     IcpScratch(u64 m, bool loop)
     {
-        size_t at = 0;
-        auto take = [&](u64 b) {
-            const size_t here = at;
-            at += padded(b);
-            return here;
-        };
-        y32 = take(m * 3 * sizeof(float));
-        order = take(m * sizeof(u32));
+        Carve c;
+        y32 = c.take(m * 3 * sizeof(float));
+        order = c.take(m * sizeof(u32));
         if (loop) {
-            state = take(sizeof(IcpState));
-            pairs0 = take(m * sizeof(uint2));
-            pairs1 = take(m * sizeof(uint2));
-            fit = take(fit_scratch_bytes());
-            plane = take(static_cast<u64>(PLANE_BLOCKS) * PLANE_STRIDE * sizeof(double));
+            state = c.take(sizeof(IcpState));
+            pairs0 = c.take(m * sizeof(uint2));
+            pairs1 = c.take(m * sizeof(uint2));
+            fit = c.take(fit_scratch_bytes());
+            plane = c.take(static_cast<u64>(FIT_BLOCKS) * PLANE_STRIDE * sizeof(double));
         }
-        bytes = at ? at : 256;
+        bytes = c.bytes() ? c.bytes() : 256;
     }
 };
 
@@ -426,11 +404,7 @@ int with_lease(Index& ix, size_t bytes, Body&& body)
     }
     DeviceShared& sh = shared_of(ix.device);
     std::lock_guard<std::mutex> lock(sh.mu);
-    ScratchLease lease(sh, ix.device, ix.stream);
-    int st;
-    if ((st = lease.take(bytes)) != PCPX_OK) return st;
-    if ((st = body(static_cast<char*>(lease.p))) != PCPX_OK) return st;
-    return lease.leave_queued();
+    return leased(sh, ix.device, ix.stream, bytes, body);
 }
 
 int nearest_device(Index& ix, const float* d_s, u64 m64, const double* d_pose, float radius, u32* d_partner, float* d_d2)
@@ -496,8 +470,7 @@ int icp_device(Index& ix, const float* d_s, u64 m64, const double* d_pose, float
             k_icp_decide<<<1, 64, 0, s>>>(state, k, plane ? 6u : 3u, m);
             if (plane) {
                 const PlaneIn in{d_s, ix.d_xyz, d_normals, pairs[k & 1u], m, static_cast<u32>(ix.n_in), {o[0], o[1], o[2]}};
-                k_plane_partial<<<PLANE_BLOCKS, ICP_BLOCK, 0, s>>>(in, state, plane_partial);
-                k_plane_final<<<1, 64, 0, s>>>(plane_partial, state);
+                fixed_sum(PlaneSystem{in, state, {}}, plane_partial, s);
                 k_plane_solve<<<1, 64, 0, s>>>(state, o[0], o[1], o[2]);
             } else if ((st = fit_pairs_device(d_s, m, ix.d_xyz, static_cast<u32>(ix.n_in), reinterpret_cast<const u32*>(pairs[k & 1u]), m,
                                               &state->fit_count, base + L.fit, state->pose, state->cand, &state->rms_cand, s)) != PCPX_OK) {

@@ -1,13 +1,29 @@
-// pcpx_lease.h -- the scratch of the entry points that take a device number and do not wait for their kernels (pcpx_match.hip,
-// pcpx_register.hip).  Included by .hip translation units only.
+// pcpx_lease.h -- the scratch of the entry points that do not wait for their kernels, and the two prologues around it: the _dev
+// forms that take a device number and a stream (pcpx_match.hip, pcpx_register.hip, pcpx_planes.hip; pcpx_icp.hip comes in with a
+// handle and its stream) and the host-pointer forms of the same files, which stage their arrays on a stream of the pool and wait.
+// Included by .hip translation units only.
 #ifndef PCPX_LEASE_H
 #define PCPX_LEASE_H
 
 #include "pcpx_internal.h"
 
+#include <deque>
 #include <vector>
 
 namespace pcpx {
+
+// Where everything lies in the scratch of a call: byte offsets from its start, each a multiple of 256.
+inline size_t padded(u64 bytes) { return (bytes + 255) / 256 * 256; }
+struct Carve {
+    size_t at = 0;
+    size_t take(u64 bytes)
+    {
+        const size_t here = at;
+        at += padded(bytes);
+        return here;
+    }
+    size_t bytes() const { return at; }
+};
 
 // A block of the device's pool goes back to the pool when the host knows that nothing queued reads it.  A _dev call returns before
 // that, so it leaves the block here with an event recorded behind its last kernel; the next such call on the device gives
@@ -72,6 +88,94 @@ struct ScratchLease {
         pool.release(p);
     }
 };
+
+// A lease of `bytes` on s around a body that only enqueues: body(base) gets the block's address, and the block stays held until
+// the stream has passed what the body queued.  The caller holds the device's DeviceShared::mu.
+template <class Body>
+int leased(DeviceShared& sh, int device, hipStream_t s, size_t bytes, Body&& body)
+{
+    ScratchLease lease(sh, device, s);
+    int st;
+    if ((st = lease.take(bytes)) != PCPX_OK) return st;
+    if ((st = body(static_cast<char*>(lease.p))) != PCPX_OK) return st;
+    return lease.leave_queued();
+}
+
+// The prologue of a _dev entry point that takes a device number and the caller's stream (after its argument checks): the device
+// made current and locked, `bytes` of scratch leased, body(base, stream).
+template <class Body>
+int on_leased(int device, const char* what, void* stream, size_t bytes, Body&& body)
+{
+    if (device < 0 || device >= LEASE_MAX_DEVICES) return select_device(device);
+    return on_shared(device, what, [&](DeviceShared& sh) -> int {
+        const hipStream_t s = static_cast<hipStream_t>(stream);
+        return leased(sh, device, s, bytes, [&](char* base) -> int { return body(base, s); });
+    });
+}
+
+// A host-pointer call on the device: a stream of the pool, the caller's arrays in blocks of the device's pool, blocks for the
+// outputs, the scratch, and the wait.  A failed step makes the later ones do nothing and stays in `st`.  The blocks go back to the
+// pool when the call ends, after the stream has been waited on (a failed call waits in the lease's destructor).
+struct HostCall {
+    DevPool& pool;
+    PooledStream ps;
+    std::deque<DevBuf> blocks;
+    ScratchLease lease;  // (last: the first to go)
+    hipStream_t s = nullptr;
+    int st = PCPX_OK;
+    HostCall(DeviceShared& sh, int device) : pool(sh.pool), lease(sh, device, nullptr) {}
+    int begin()
+    {
+        PCPX_HIP(pooled_stream_get(&ps.s));
+        s = lease.stream = ps.s;
+        return PCPX_OK;
+    }
+    // `bytes` of device memory; null for none
+    void* alloc(size_t bytes)
+    {
+        if (st != PCPX_OK || !bytes) return nullptr;
+        blocks.emplace_back(pool);
+        st = blocks.back().alloc(bytes);
+        return blocks.back().p;
+    }
+    template <class T>
+    T* alloc(size_t bytes) { return static_cast<T*>(alloc(bytes)); }
+    // this host array of this many bytes on the device, or null when there is none
+    template <class T>
+    const T* upload(const T* host, size_t bytes)
+    {
+        void* d = host ? alloc(bytes) : nullptr;
+        if (d && st == PCPX_OK) st = upload_pageable(d, host, bytes, s);
+        return static_cast<const T*>(d);
+    }
+    char* scratch(size_t bytes)
+    {
+        if (st == PCPX_OK) st = lease.take(bytes);
+        return static_cast<char*>(lease.p);
+    }
+    int download(void* host, const void* d, size_t bytes)
+    {
+        PCPX_HIP(hipMemcpyAsync(host, d, bytes, hipMemcpyDeviceToHost, s));
+        return PCPX_OK;
+    }
+    int wait()
+    {
+        PCPX_HIP(hipStreamSynchronize(s));
+        return PCPX_OK;
+    }
+};
+
+// The prologue of a host-pointer entry point that takes a device number (after its argument checks): body(call).
+template <class Body>
+int on_host_call(int device, const char* what, Body&& body)
+{
+    if (device < 0 || device >= LEASE_MAX_DEVICES) return select_device(device);
+    return on_shared(device, what, [&](DeviceShared& sh) -> int {
+        HostCall call(sh, device);
+        const int st = call.begin();
+        return st != PCPX_OK ? st : body(call);
+    });
+}
 
 }  // namespace pcpx
 

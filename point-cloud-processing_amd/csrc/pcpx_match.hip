@@ -30,6 +30,8 @@ static_assert(PCPX_MATCH_NONE == MT_PAD, "no match = the padding key's index");
 // (a wave's prologue -- its source rows, W loads per lane -- is paid per segment) and there are never more than MT_MAX_SEGMENTS
 // (k_match_merge reads 16 bytes per source and segment, one thread per source).  Segment lengths are multiples of
 // MT_MIN_SEGMENT_ROWS, so the last segment is whatever is left: anything from one row to a full segment.
+// (segment_plan of pcpx_ransac.h has this formula and these values.  This file keeps its own: that header defines k_ransac_best and
+// k_reg_compact, which would be compiled into this file with it and are no part of a matching call.)
 constexpr u64 MT_TARGET_WAVES = 16384;
 constexpr u64 MT_MAX_SEGMENTS = 256;
 constexpr u64 MT_MIN_SEGMENT_ROWS = 256;
@@ -44,7 +46,6 @@ inline u32 width_for(u32 dims)
 }
 
 inline u32 blocks_of(u64 n, u32 per) { return static_cast<u32>((n + per - 1) / per); }
-inline size_t padded(u64 bytes) { return (bytes + 255) / 256 * 256; }
 
 struct Split {
     u32 segments = 0;
@@ -74,26 +75,21 @@ struct Layout {
     {
         width = width_for(dims);
         fwd = split_for(m, n), rev = split_for(n, m);
-        size_t at = 0;
-        auto take = [&](u64 b) {
-            const size_t here = at;
-            at += padded(b);
-            return here;
-        };
-        tgt_rec = take(n * width * sizeof(float));
-        src_rec = take(m * width * sizeof(float));
-        tgt_valid = take(n);
-        src_valid = take(m);
+        Carve c;
+        tgt_rec = c.take(n * width * sizeof(float));
+        src_rec = c.take(m * width * sizeof(float));
+        tgt_valid = c.take(n);
+        src_valid = c.take(m);
         // two keys per (row on a lane, segment): the larger of the two directions, which run one after the other
-        part = take(std::max<u64>(static_cast<u64>(fwd.segments) * m, static_cast<u64>(rev.segments) * n) * 2 * sizeof(u64));
-        best_idx = take(m * sizeof(u32));
-        best_d2 = take(m * sizeof(float));
-        second_d2 = take(m * sizeof(float));
-        rev_idx = take(n * sizeof(u32));
-        keep = take(m);
-        place = take(m * sizeof(u32));
-        sums = take(static_cast<u64>(scan_tiles(m)) * sizeof(u32));
-        bytes = at;
+        part = c.take(std::max<u64>(static_cast<u64>(fwd.segments) * m, static_cast<u64>(rev.segments) * n) * 2 * sizeof(u64));
+        best_idx = c.take(m * sizeof(u32));
+        best_d2 = c.take(m * sizeof(float));
+        second_d2 = c.take(m * sizeof(float));
+        rev_idx = c.take(n * sizeof(u32));
+        keep = c.take(m);
+        place = c.take(m * sizeof(u32));
+        sums = c.take(static_cast<u64>(scan_tiles(m)) * sizeof(u32));
+        bytes = c.bytes();
     }
 };
 
@@ -351,21 +347,6 @@ int check_ratio(const char* what, float max_ratio_sq)
     return PCPX_ERR_INVALID;
 }
 
-// the two sets of a host-form call on the device
-struct Staged {
-    DevBuf src, tgt;
-    explicit Staged(DevPool& pool) : src(pool), tgt(pool) {}
-    int upload(const float* h_src, u64 m, const float* h_tgt, u64 n, u32 dims, hipStream_t s)
-    {
-        int st;
-        if (m && ((st = src.alloc(m * dims * sizeof(float))) != PCPX_OK || (st = upload_pageable(src.p, h_src, m * dims * sizeof(float), s)) != PCPX_OK))
-            return st;
-        if (n && ((st = tgt.alloc(n * dims * sizeof(float))) != PCPX_OK || (st = upload_pageable(tgt.p, h_tgt, n * dims * sizeof(float), s)) != PCPX_OK))
-            return st;
-        return PCPX_OK;
-    }
-};
-
 }  // namespace
 
 }  // namespace pcpx
@@ -397,17 +378,9 @@ int pcpx_match_nearest_dev(const float* d_src, uint64_t m, const float* d_tgt, u
     static const char* what = "pcpx_match_nearest_dev";
     int st = check_match_args(what, d_src, m, d_tgt, n, dims, flags, PCPX_MATCH_SKIP_ZERO_ROWS, d_out_idx);
     if (st != PCPX_OK || m == 0) return st;
-    if (device < 0 || device >= LEASE_MAX_DEVICES) return select_device(device);
-    return on_shared(device, what, [&](DeviceShared& sh) -> int {
-        const hipStream_t s = static_cast<hipStream_t>(stream);
-        const Layout L(m, n, dims);
-        ScratchLease lease(sh, device, s);
-        int r;
-        if ((r = lease.take(L.bytes)) != PCPX_OK) return r;
-        if ((r = nearest_device(L, static_cast<char*>(lease.p), d_src, m, d_tgt, n, dims, flags, s, d_out_idx, d_opt_out_d2, d_opt_out_second_idx,
-                                d_opt_out_second_d2)) != PCPX_OK)
-            return r;
-        return lease.leave_queued();
+    const Layout L(m, n, dims);
+    return on_leased(device, what, stream, L.bytes, [&](char* base, hipStream_t s) -> int {
+        return nearest_device(L, base, d_src, m, d_tgt, n, dims, flags, s, d_out_idx, d_opt_out_d2, d_opt_out_second_idx, d_opt_out_second_d2);
     });
 }
 
@@ -417,29 +390,22 @@ int pcpx_match_nearest(const float* src, uint64_t m, const float* tgt, uint64_t 
     static const char* what = "pcpx_match_nearest";
     int st = check_match_args(what, src, m, tgt, n, dims, flags, PCPX_MATCH_SKIP_ZERO_ROWS, out_idx);
     if (st != PCPX_OK || m == 0) return st;
-    if (device < 0 || device >= LEASE_MAX_DEVICES) return select_device(device);
-    return on_shared(device, what, [&](DeviceShared& sh) -> int {
-        PooledStream ps;
-        PCPX_HIP(pooled_stream_get(&ps.s));
-        const hipStream_t s = ps.s;
+    return on_host_call(device, what, [&](HostCall& call) -> int {
         const Layout L(m, n, dims);
-        Staged in(sh.pool);
-        DevBuf di(sh.pool), dd(sh.pool), dsi(sh.pool), dsd(sh.pool);
-        ScratchLease lease(sh, device, s);
+        const float* d_src = call.upload(src, m * dims * sizeof(float));
+        const float* d_tgt = call.upload(tgt, n * dims * sizeof(float));
+        u32* di = call.alloc<u32>(m * sizeof(u32));
+        float* dd = opt_out_d2 ? call.alloc<float>(m * sizeof(float)) : nullptr;
+        u32* dsi = opt_out_second_idx ? call.alloc<u32>(m * sizeof(u32)) : nullptr;
+        float* dsd = opt_out_second_d2 ? call.alloc<float>(m * sizeof(float)) : nullptr;
+        char* base = call.scratch(L.bytes);
         int r;
-        if ((r = in.upload(src, m, tgt, n, dims, s)) != PCPX_OK || (r = di.alloc(m * sizeof(u32))) != PCPX_OK ||
-            (opt_out_d2 && (r = dd.alloc(m * sizeof(float))) != PCPX_OK) || (opt_out_second_idx && (r = dsi.alloc(m * sizeof(u32))) != PCPX_OK) ||
-            (opt_out_second_d2 && (r = dsd.alloc(m * sizeof(float))) != PCPX_OK) || (r = lease.take(L.bytes)) != PCPX_OK)
+        if ((r = call.st) != PCPX_OK || (r = nearest_device(L, base, d_src, m, d_tgt, n, dims, flags, call.s, di, dd, dsi, dsd)) != PCPX_OK ||
+            (r = call.download(out_idx, di, m * sizeof(u32))) != PCPX_OK || (dd && (r = call.download(opt_out_d2, dd, m * sizeof(float))) != PCPX_OK) ||
+            (dsi && (r = call.download(opt_out_second_idx, dsi, m * sizeof(u32))) != PCPX_OK) ||
+            (dsd && (r = call.download(opt_out_second_d2, dsd, m * sizeof(float))) != PCPX_OK))
             return r;
-        if ((r = nearest_device(L, static_cast<char*>(lease.p), in.src.as<float>(), m, in.tgt.as<float>(), n, dims, flags, s, di.as<u32>(), dd.as<float>(),
-                                dsi.as<u32>(), dsd.as<float>())) != PCPX_OK)
-            return r;
-        PCPX_HIP(hipMemcpyAsync(out_idx, di.p, m * sizeof(u32), hipMemcpyDeviceToHost, s));
-        if (opt_out_d2) PCPX_HIP(hipMemcpyAsync(opt_out_d2, dd.p, m * sizeof(float), hipMemcpyDeviceToHost, s));
-        if (opt_out_second_idx) PCPX_HIP(hipMemcpyAsync(opt_out_second_idx, dsi.p, m * sizeof(u32), hipMemcpyDeviceToHost, s));
-        if (opt_out_second_d2) PCPX_HIP(hipMemcpyAsync(opt_out_second_d2, dsd.p, m * sizeof(float), hipMemcpyDeviceToHost, s));
-        PCPX_HIP(hipStreamSynchronize(s));
-        return PCPX_OK;
+        return call.wait();
     });
 }
 
@@ -451,18 +417,16 @@ int pcpx_match_correspondences_dev(const float* d_src, uint64_t m, const float* 
     int st = check_match_args(what, d_src, m, d_tgt, n, dims, flags, PCPX_MATCH_SKIP_ZERO_ROWS | PCPX_MATCH_MUTUAL, d_out_pairs);
     if (st != PCPX_OK || (st = check_ratio(what, max_ratio_sq)) != PCPX_OK) return st;
     if (m == 0 && !d_opt_out_count) return PCPX_OK;
-    if (device < 0 || device >= LEASE_MAX_DEVICES) return select_device(device);
-    return on_shared(device, what, [&](DeviceShared& sh) -> int {
-        const hipStream_t s = static_cast<hipStream_t>(stream);
-        const Layout L(m, n, dims);
-        if (m == 0) return correspondences_device(L, nullptr, d_src, m, d_tgt, n, dims, max_ratio_sq, flags, s, d_out_pairs, d_opt_out_d2, d_opt_out_count);
-        ScratchLease lease(sh, device, s);
-        int r;
-        if ((r = lease.take(L.bytes)) != PCPX_OK) return r;
-        if ((r = correspondences_device(L, static_cast<char*>(lease.p), d_src, m, d_tgt, n, dims, max_ratio_sq, flags, s, d_out_pairs, d_opt_out_d2,
-                                        d_opt_out_count)) != PCPX_OK)
-            return r;
-        return lease.leave_queued();
+    const Layout L(m, n, dims);
+    if (m == 0) {  // (only the count word is cleared: no scratch)
+        if (device < 0 || device >= LEASE_MAX_DEVICES) return select_device(device);
+        return on_shared(device, what, [&](DeviceShared&) -> int {
+            return correspondences_device(L, nullptr, d_src, m, d_tgt, n, dims, max_ratio_sq, flags, static_cast<hipStream_t>(stream), d_out_pairs, d_opt_out_d2,
+                                          d_opt_out_count);
+        });
+    }
+    return on_leased(device, what, stream, L.bytes, [&](char* base, hipStream_t s) -> int {
+        return correspondences_device(L, base, d_src, m, d_tgt, n, dims, max_ratio_sq, flags, s, d_out_pairs, d_opt_out_d2, d_opt_out_count);
     });
 }
 
@@ -477,29 +441,23 @@ int pcpx_match_correspondences(const float* src, uint64_t m, const float* tgt, u
     *out_count = 0;
     int st = check_match_args(what, src, m, tgt, n, dims, flags, PCPX_MATCH_SKIP_ZERO_ROWS | PCPX_MATCH_MUTUAL, out_pairs);
     if (st != PCPX_OK || (st = check_ratio(what, max_ratio_sq)) != PCPX_OK || m == 0) return st;
-    if (device < 0 || device >= LEASE_MAX_DEVICES) return select_device(device);
-    return on_shared(device, what, [&](DeviceShared& sh) -> int {
-        PooledStream ps;
-        PCPX_HIP(pooled_stream_get(&ps.s));
-        const hipStream_t s = ps.s;
+    return on_host_call(device, what, [&](HostCall& call) -> int {
         const Layout L(m, n, dims);
-        Staged in(sh.pool);
-        DevBuf dp(sh.pool), dd(sh.pool), dc(sh.pool);
-        ScratchLease lease(sh, device, s);
-        int r;
-        if ((r = in.upload(src, m, tgt, n, dims, s)) != PCPX_OK || (r = dp.alloc(m * 2 * sizeof(u32))) != PCPX_OK ||
-            (opt_out_d2 && (r = dd.alloc(m * sizeof(float))) != PCPX_OK) || (r = dc.alloc(sizeof(u64))) != PCPX_OK || (r = lease.take(L.bytes)) != PCPX_OK)
-            return r;
-        if ((r = correspondences_device(L, static_cast<char*>(lease.p), in.src.as<float>(), m, in.tgt.as<float>(), n, dims, max_ratio_sq, flags, s,
-                                        dp.as<u32>(), dd.as<float>(), dc.as<u64>())) != PCPX_OK)
-            return r;
+        const float* d_src = call.upload(src, m * dims * sizeof(float));
+        const float* d_tgt = call.upload(tgt, n * dims * sizeof(float));
+        u32* dp = call.alloc<u32>(m * 2 * sizeof(u32));
+        float* dd = opt_out_d2 ? call.alloc<float>(m * sizeof(float)) : nullptr;
+        u64* dc = call.alloc<u64>(sizeof(u64));
+        char* base = call.scratch(L.bytes);
         u64 count = 0;
-        PCPX_HIP(hipMemcpyAsync(&count, dc.p, sizeof(u64), hipMemcpyDeviceToHost, s));
-        PCPX_HIP(hipStreamSynchronize(s));
+        int r;
+        if ((r = call.st) != PCPX_OK || (r = correspondences_device(L, base, d_src, m, d_tgt, n, dims, max_ratio_sq, flags, call.s, dp, dd, dc)) != PCPX_OK ||
+            (r = call.download(&count, dc, sizeof(u64))) != PCPX_OK || (r = call.wait()) != PCPX_OK)
+            return r;
         if (count) {
-            PCPX_HIP(hipMemcpyAsync(out_pairs, dp.p, count * 2 * sizeof(u32), hipMemcpyDeviceToHost, s));
-            if (opt_out_d2) PCPX_HIP(hipMemcpyAsync(opt_out_d2, dd.p, count * sizeof(float), hipMemcpyDeviceToHost, s));
-            PCPX_HIP(hipStreamSynchronize(s));
+            if ((r = call.download(out_pairs, dp, count * 2 * sizeof(u32))) != PCPX_OK ||
+                (dd && (r = call.download(opt_out_d2, dd, count * sizeof(float))) != PCPX_OK) || (r = call.wait()) != PCPX_OK)
+                return r;
         }
         *out_count = count;
         return PCPX_OK;

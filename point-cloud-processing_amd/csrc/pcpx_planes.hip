@@ -10,8 +10,8 @@
 //   k_plane_decide   one thread: the winner rebuilt by the same device function, found / stop, the plane in float64
 //   k_plane_flag     the inlier flag and the keep flag of every live record, the label of the inliers' rows
 //   pcpx_scan.h, k_reg_compact (pcpx_ransac.h), k_plane_rows     the inliers' rows in record order
-//   k_pfit_partial / k_pfit_final / k_pfit_solve   the float64 sums of the plane fit in pcpx_ransac.h's fixed order, and the
-//                    smallest eigenvector (pcpx_plane_fit.h)
+//   k_fixed_partial / k_fixed_final (pcpx_fixed_sum.h) over PlaneSum<1..3>, k_pfit_solve   the float64 sums of the plane fit in the
+//                    fixed order, and the smallest eigenvector (pcpx_plane_fit.h)
 //   pcpx_scan.h, k_plane_keep    the records that are not inliers, in order, into the other buffer: the next round's
 // Every kernel of round r returns at once when the loop stopped in an earlier round (State::done).
 #include "pcpx_device.h"
@@ -33,16 +33,11 @@ namespace {
 
 constexpr u32 PL_FOLD = 16;  // lanes of k_plane_fold that share a hypothesis
 constexpr u32 PL_WAVES = 4;  // waves of a k_plane_count block: four consecutive hypothesis groups on one segment (they share its records in the scalar cache)
-// The plan is pcpx_register.hip's, for its reasons: about PL_TARGET_WAVES waves a call, segments of PL_MIN_SEGMENT_ROWS records at
-// the least (a wave's prologue -- three gathers, a root and a division -- is paid per segment), PL_MAX_SEGMENTS at the most.
-constexpr u64 PL_TARGET_WAVES = 16384;
-constexpr u64 PL_MAX_SEGMENTS = 256;
-constexpr u64 PL_MIN_SEGMENT_ROWS = 256;
-constexpr u64 PL_LAUNCH_HYPOTHESES = 1ull << 30;  // hypotheses of one launch (a grid's thread count stays below 2^32)
+// (the plan -- segment_plan and its constants --: pcpx_ransac.h)
 // the doubles of the fit's state: [0] the number of usable rows, [1..3] the sums, [4..6] the centroid, [8..13] the scatter,
 // [16] the sum of squared residuals, [20..23] the plane
 constexpr u32 PF_STATE = 32, PF_N = 0, PF_SUM = 1, PF_C = 4, PF_S = 8, PF_SS = 16, PF_PLANE = 20;
-constexpr size_t PFIT_SCRATCH_BYTES = (static_cast<size_t>(FIT_BLOCKS) * FIT_TERMS + PF_STATE) * sizeof(double);
+constexpr size_t PFIT_SCRATCH_BYTES = fit_bytes(PF_STATE);
 
 struct Rec16 {
     float v[4];  // x - o, the row's bits
@@ -80,39 +75,26 @@ __device__ __forceinline__ bool gone(const u32* done, u32 round)
 }
 
 struct Layout {
-    u32 segments = 0;
-    u64 rows = 0;  // per segment
+    SegmentPlan plan;
     size_t rec[2] = {0, 0}, counts = 0, key = 0, flag = 0, keep = 0, place = 0, sums = 0, positions = 0, rowsout = 0, npos = 0, state = 0, fit = 0, bytes = 0;
-    Layout(u64 hypotheses, u64 capacity, bool normals, bool peel)
+    Layout(u64 hypotheses, u64 capacity, bool normals, bool peel) : plan(segment_plan(hypotheses, capacity))
     {
-        if (capacity) {
-            const u64 groups = std::max<u64>(1, (hypotheses + GROUP - 1) / GROUP);
-            const u64 want = (PL_TARGET_WAVES + groups - 1) / groups;
-            const u64 s0 = std::max<u64>(1, std::min({want, PL_MAX_SEGMENTS, capacity / PL_MIN_SEGMENT_ROWS}));
-            rows = ((capacity + s0 - 1) / s0 + PL_MIN_SEGMENT_ROWS - 1) / PL_MIN_SEGMENT_ROWS * PL_MIN_SEGMENT_ROWS;
-            segments = static_cast<u32>((capacity + rows - 1) / rows);
-        }
-        size_t at = 0;
-        auto take = [&](u64 b) {
-            const size_t here = at;
-            at += padded(b);
-            return here;
-        };
+        Carve c;
         const u64 rec_bytes = normals ? sizeof(Rec32) : sizeof(Rec16);
-        rec[0] = take(capacity * rec_bytes);
-        rec[1] = peel ? take(capacity * rec_bytes) : rec[0];
-        counts = take(hypotheses * segments * sizeof(u32));
-        key = take(sizeof(u64));
-        flag = take(capacity);
-        keep = take(capacity);
-        place = take(capacity * sizeof(u32));
-        sums = take(static_cast<u64>(scan_tiles(capacity)) * sizeof(u32));
-        positions = take(capacity * sizeof(u32));
-        rowsout = take(capacity * sizeof(u32));
-        npos = take(sizeof(u64));
-        state = take(sizeof(State));
-        fit = take(PFIT_SCRATCH_BYTES);
-        bytes = at;
+        rec[0] = c.take(capacity * rec_bytes);
+        rec[1] = peel ? c.take(capacity * rec_bytes) : rec[0];
+        counts = c.take(hypotheses * plan.segments * sizeof(u32));
+        key = c.take(sizeof(u64));
+        flag = c.take(capacity);
+        keep = c.take(capacity);
+        place = c.take(capacity * sizeof(u32));
+        sums = c.take(static_cast<u64>(scan_tiles(capacity)) * sizeof(u32));
+        positions = c.take(capacity * sizeof(u32));
+        rowsout = c.take(capacity * sizeof(u32));
+        npos = c.take(sizeof(u64));
+        state = c.take(sizeof(State));
+        fit = c.take(PFIT_SCRATCH_BYTES);
+        bytes = c.bytes();
     }
 };
 
@@ -123,12 +105,7 @@ struct Cloud {
     const u32* rows;       // null: all n rows in order
     const u64* d_count;    // null: capacity
     u32 n, capacity, origin_row;
-    __device__ __forceinline__ u32 count() const
-    {
-        if (!d_count) return capacity;
-        const u64 c = *d_count;
-        return c < capacity ? static_cast<u32>(c) : capacity;
-    }
+    __device__ __forceinline__ u32 count() const { return clamped_count(d_count, capacity); }
     __device__ __forceinline__ u32 row_of(u32 k) const { return rows ? rows[k] : k; }
     // the coordinates (and under the gate the normal) of a row of points; false when it is not usable
     __device__ __forceinline__ bool load(u32 row, float (&x)[3], float (&nn)[3]) const
@@ -423,13 +400,7 @@ struct FitRows {
     const u64* d_count;    // null: capacity
     u32 n, capacity;
     bool listed;
-    __device__ __forceinline__ u32 items() const
-    {
-        if (!listed) return n;
-        if (!d_count) return capacity;
-        const u64 c = *d_count;
-        return c < capacity ? static_cast<u32>(c) : capacity;
-    }
+    __device__ __forceinline__ u32 items() const { return listed ? clamped_count(d_count, capacity) : n; }
     __device__ __forceinline__ bool load(u32 j, double (&x)[3]) const
     {
         const u32 row = listed ? rows[j] : j;
@@ -445,23 +416,23 @@ struct FitRows {
     }
 };
 
-constexpr int pfit_terms(int pass) { return pass == 1 ? 4 : pass == 2 ? 6 : 1; }
-
-// Pass 1: the number of usable rows and the sums of their coordinates.  Pass 2: the scatter about the centroid.  Pass 3: the squared
-// distances from the plane.  The order of the sums is pcpx_ransac.h's.
+// The three sums of the fit, in pcpx_fixed_sum.h's order.  Pass 1: the number of usable rows and the sums of their coordinates, and
+// from them the centroid.  Pass 2: the scatter about the centroid.  Pass 3: the squared distances from the plane, and from them the
+// root mean square (NaN with fewer than three usable rows).  A launch of a round after the loop stopped writes nothing.
 template <int PASS>
-__global__ __launch_bounds__(RG_BLOCK) void k_pfit_partial(FitRows set, const u32* __restrict__ done, u32 round, const double* __restrict__ state,
-                                                          double* __restrict__ partial)
-{
-    constexpr int NT = pfit_terms(PASS);
-    if (gone(done, round)) return;  // (block-uniform)
-    const u32 n = set.items();
-    double acc[NT];
-#pragma unroll
-    for (int i = 0; i < NT; ++i) acc[i] = 0.0;
-    for (u64 j = static_cast<u64>(blockIdx.x) * RG_BLOCK + threadIdx.x; j < n; j += static_cast<u64>(gridDim.x) * RG_BLOCK) {
+struct PlaneSum {
+    static constexpr int TERMS = PASS == 1 ? 4 : PASS == 2 ? 6 : 1, STRIDE = FIT_TERMS;
+    FitRows set;
+    const u32* done;
+    u32 round;
+    double* state;
+    double* out_rms;  // (pass 3)
+    __device__ __forceinline__ bool live() const { return !gone(done, round); }
+    __device__ __forceinline__ u32 items() const { return set.items(); }
+    __device__ __forceinline__ void add(u32 j, double (&acc)[TERMS]) const
+    {
         double x[3];
-        if (!set.load(static_cast<u32>(j), x)) continue;
+        if (!set.load(j, x)) return;
         if constexpr (PASS == 1) {
             acc[0] += 1.0;
 #pragma unroll
@@ -475,29 +446,26 @@ __global__ __launch_bounds__(RG_BLOCK) void k_pfit_partial(FitRows set, const u3
             acc[0] += e * e;
         }
     }
-    fit_block_sums<NT>(acc, partial);
-}
-
-template <int PASS>
-__global__ __launch_bounds__(64) void k_pfit_final(const double* __restrict__ partial, u32 nblocks, const u32* __restrict__ done, u32 round,
-                                                  double* __restrict__ state, double* __restrict__ out_rms)
-{
-    constexpr int NT = pfit_terms(PASS);
-    if (gone(done, round) || threadIdx.x >= NT) return;
-    const double sum = fit_sum_blocks(partial, nblocks, threadIdx.x);
-    if constexpr (PASS == 1) {
-        const double n = __shfl(sum, 0);
-        state[PF_N + threadIdx.x] = sum;  // (PF_SUM = PF_N + 1)
-        if (threadIdx.x >= 1) state[PF_C + threadIdx.x - 1] = n > 0.0 ? sum / n : 0.0;
-    } else if constexpr (PASS == 2) {
-        state[PF_S + threadIdx.x] = sum;
-    } else {
-        const double n = state[PF_N];
-        state[PF_SS] = sum;
-        *out_rms = n >= 3.0 ? std::sqrt(sum / n) : std::numeric_limits<double>::quiet_NaN();
+    __device__ __forceinline__ void finish(u32 term, double sum) const
+    {
+        if constexpr (PASS == 1) {
+            const double n = __shfl(sum, 0);
+            state[PF_N + term] = sum;  // (PF_SUM = PF_N + 1)
+            if (term >= 1) state[PF_C + term - 1] = n > 0.0 ? sum / n : 0.0;
+        } else if constexpr (PASS == 2) {
+            state[PF_S + term] = sum;
+        } else {
+            const double n = state[PF_N];
+            state[PF_SS] = sum;
+            *out_rms = n >= 3.0 ? std::sqrt(sum / n) : std::numeric_limits<double>::quiet_NaN();
+        }
     }
-}
-static_assert(PF_SUM == PF_N + 1, "k_pfit_final<1> writes them as one run");
+};
+static_assert(PF_SUM == PF_N + 1, "pass 1 writes them as one run");
+// (named, not PlaneSum<1>: a kernel then reads k_fixed_partial<PlaneCentroid> in a profile)
+struct PlaneCentroid : PlaneSum<1> {};
+struct PlaneScatter : PlaneSum<2> {};
+struct PlaneResiduals : PlaneSum<3> {};
 
 // One thread: the normal from the scatter, d = -n . c.  hyp (optional, 4 doubles): the hypothesis of a RANSAC refit -- the normal's
 // sign follows it, and it is the result with fewer than three usable rows (else zeros).
@@ -525,22 +493,15 @@ __global__ __launch_bounds__(64) void k_pfit_solve(double* __restrict__ state, c
     }
 }
 
-// The fit, enqueued on s.  scratch: PFIT_SCRATCH_BYTES.  The grid is always FIT_BLOCKS blocks, so the order of the sums -- and with
-// it every bit of the result -- depends on the list alone, not on the capacities of the call.
+// The fit, enqueued on s.  scratch: PFIT_SCRATCH_BYTES.
 int pfit_device(const FitRows& set, char* scratch, const u32* d_done, u32 round, const double* d_hyp, double* d_out, double* d_out_rms, hipStream_t s)
 {
     double* partial = reinterpret_cast<double*>(scratch);
     double* state = partial + static_cast<size_t>(FIT_BLOCKS) * FIT_TERMS;
-    const u32 blocks = FIT_BLOCKS;
-    k_pfit_partial<1><<<blocks, RG_BLOCK, 0, s>>>(set, d_done, round, state, partial);
-    k_pfit_final<1><<<1, 64, 0, s>>>(partial, blocks, d_done, round, state, nullptr);
-    k_pfit_partial<2><<<blocks, RG_BLOCK, 0, s>>>(set, d_done, round, state, partial);
-    k_pfit_final<2><<<1, 64, 0, s>>>(partial, blocks, d_done, round, state, nullptr);
+    fixed_sum(PlaneCentroid{{set, d_done, round, state, nullptr}}, partial, s);
+    fixed_sum(PlaneScatter{{set, d_done, round, state, nullptr}}, partial, s);
     k_pfit_solve<<<1, 64, 0, s>>>(state, d_done, round, d_hyp, d_out);
-    if (d_out_rms) {
-        k_pfit_partial<3><<<blocks, RG_BLOCK, 0, s>>>(set, d_done, round, state, partial);
-        k_pfit_final<3><<<1, 64, 0, s>>>(partial, blocks, d_done, round, state, d_out_rms);
-    }
+    if (d_out_rms) fixed_sum(PlaneResiduals{{set, d_done, round, state, d_out_rms}}, partial, s);
     PCPX_HIP(hipGetLastError());
     return PCPX_OK;
 }
@@ -586,12 +547,12 @@ int planes_device(const Layout& L, char* base, const Cloud& in, const pcpx_plane
         const u32 seed = single ? a.seed : fmix32(a.seed + round);
         PCPX_HIP(hipMemsetAsync(key, 0, sizeof(u64), s));
         if (cap) {
-            for (u64 h0 = 0; h0 < T; h0 += PL_LAUNCH_HYPOTHESES) {
-                const u64 here = std::min(PL_LAUNCH_HYPOTHESES, T - h0);
-                const dim3 grid(blocks_of((here + GROUP - 1) / GROUP, PL_WAVES), L.segments);
+            for (u64 h0 = 0; h0 < T; h0 += PLAN_LAUNCH_HYPOTHESES) {
+                const u64 here = std::min(PLAN_LAUNCH_HYPOTHESES, T - h0);
+                const dim3 grid(blocks_of((here + GROUP - 1) / GROUP, PL_WAVES), L.plan.segments);
                 k_plane_count<NORMALS><<<grid, 64 * PL_WAVES, 0, s>>>(rec[cur], cap, &st->live[cur], &st->done, round, h0, T, seed, gate, a.max_distance,
-                                                                     a.min_normal_cos, L.rows, counts);
-                if (L.segments > 1) k_plane_fold<<<blocks_of(here * PL_FOLD, RG_BLOCK), RG_BLOCK, 0, s>>>(counts, &st->done, round, h0, h0 + here, T, L.segments);
+                                                                     a.min_normal_cos, L.plan.rows, counts);
+                if (L.plan.segments > 1) k_plane_fold<<<blocks_of(here * PL_FOLD, RG_BLOCK), RG_BLOCK, 0, s>>>(counts, &st->done, round, h0, h0 + here, T, L.plan.segments);
                 k_ransac_best<<<blocks_of(here, RG_BLOCK * RG_BEST_PER_THREAD), RG_BLOCK, 0, s>>>(counts, h0, h0 + here, T, 1u, key);
             }
         }
@@ -737,22 +698,6 @@ int check_pfit(const char* what, const void* out)
     return PCPX_OK;
 }
 
-// the cloud of a host-form call on the device
-struct Staged {
-    DevBuf points, normals, rows;
-    explicit Staged(DevPool& pool) : points(pool), normals(pool), rows(pool) {}
-    int upload(const float* h_points, u64 n, const float* h_normals, const u32* h_rows, u64 count, hipStream_t s)
-    {
-        int st;
-        const size_t cloud = n * 3 * sizeof(float);
-        if (n && ((st = points.alloc(cloud)) != PCPX_OK || (st = upload_pageable(points.p, h_points, cloud, s)) != PCPX_OK)) return st;
-        if (n && h_normals && ((st = normals.alloc(cloud)) != PCPX_OK || (st = upload_pageable(normals.p, h_normals, cloud, s)) != PCPX_OK)) return st;
-        if (count && h_rows && ((st = rows.alloc(count * sizeof(u32))) != PCPX_OK || (st = upload_pageable(rows.p, h_rows, count * sizeof(u32), s)) != PCPX_OK))
-            return st;
-        return PCPX_OK;
-    }
-};
-
 inline const float* gate_normals(const pcpx_plane_params* a, const float* normals) { return (a->flags & PCPX_PLANE_NORMALS) ? normals : nullptr; }
 
 }  // namespace
@@ -781,8 +726,8 @@ int pcpx_plane_plan(uint64_t hypotheses, uint64_t rows_capacity, uint32_t flags,
             return PCPX_ERR_INVALID;
         }
         const Layout L(hypotheses, rows_capacity, (flags & PCPX_PLANE_NORMALS) != 0, max_planes > 1);
-        if (out_segments) *out_segments = L.segments;
-        if (out_segment_rows) *out_segment_rows = L.rows;
+        if (out_segments) *out_segments = L.plan.segments;
+        if (out_segment_rows) *out_segment_rows = L.plan.rows;
         if (out_scratch_bytes) *out_scratch_bytes = L.bytes;
         return PCPX_OK;
     });
@@ -797,20 +742,14 @@ int pcpx_plane_ransac_dev(const float* d_points, uint64_t n, const float* d_opt_
     int st = check_cloud(what, d_points, n, d_opt_rows, rows_capacity);
     if (st != PCPX_OK || (st = check_params(what, params, d_opt_normals, n)) != PCPX_OK || (st = check_single(what, params, d_out_found, d_opt_out_refit)) != PCPX_OK)
         return st;
-    if (device < 0 || device >= LEASE_MAX_DEVICES) return select_device(device);
-    return on_shared(device, what, [&](DeviceShared& sh) -> int {
-        const hipStream_t s = static_cast<hipStream_t>(stream);
-        const u64 capacity = d_opt_rows ? rows_capacity : n;
-        const Layout L(params->hypotheses, capacity, (params->flags & PCPX_PLANE_NORMALS) != 0, false);
+    const u64 capacity = d_opt_rows ? rows_capacity : n;
+    const Layout L(params->hypotheses, capacity, (params->flags & PCPX_PLANE_NORMALS) != 0, false);
+    return on_leased(device, what, stream, L.bytes, [&](char* base, hipStream_t s) -> int {
         const Cloud in{d_points, gate_normals(params, d_opt_normals), d_opt_rows, d_opt_rows ? d_opt_rows_count : nullptr, static_cast<u32>(n),
                        static_cast<u32>(capacity), params->origin_row};
-        ScratchLease lease(sh, device, s);
-        int r;
-        if ((r = lease.take(L.bytes)) != PCPX_OK) return r;
         const PlaneOut out{d_out_found, d_opt_out_hypothesis, d_opt_out_score, d_opt_out_inliers, d_opt_out_inlier_count, d_opt_out_plane, d_opt_out_refit,
                            nullptr, nullptr, nullptr};
-        if ((r = run_planes(L, static_cast<char*>(lease.p), in, *params, 0, out, s)) != PCPX_OK) return r;
-        return lease.leave_queued();
+        return run_planes(L, base, in, *params, 0, out, s);
     });
 }
 
@@ -822,45 +761,25 @@ int pcpx_plane_ransac(const float* points, uint64_t n, const float* opt_normals,
     int st = check_cloud(what, points, n, opt_rows, rows_count);
     if (st != PCPX_OK || (st = check_params(what, params, opt_normals, n)) != PCPX_OK || (st = check_single(what, params, out_found, opt_out_refit)) != PCPX_OK)
         return st;
-    if (device < 0 || device >= LEASE_MAX_DEVICES) return select_device(device);
-    return on_shared(device, what, [&](DeviceShared& sh) -> int {
-        PooledStream ps;
-        PCPX_HIP(pooled_stream_get(&ps.s));
-        const hipStream_t s = ps.s;
+    return on_host_call(device, what, [&](HostCall& call) -> int {
         const u64 capacity = opt_rows ? rows_count : n;
         const bool gated = (params->flags & PCPX_PLANE_NORMALS) != 0, refit = (params->flags & PCPX_PLANE_REFIT) != 0;
         const Layout L(params->hypotheses, capacity, gated, false);
-        Staged in(sh.pool);
-        DevBuf small(sh.pool), inl(sh.pool);
-        ScratchLease lease(sh, device, s);
-        struct Small {
-            u32 found, h, score, pad;
-            double plane[4], refit[4];
-        } host;
-        int r;
-        if ((r = in.upload(points, n, gated ? opt_normals : nullptr, opt_rows, rows_count, s)) != PCPX_OK || (r = small.alloc(sizeof(Small))) != PCPX_OK ||
-            (opt_out_inliers && capacity && (r = inl.alloc(capacity * sizeof(u32))) != PCPX_OK) || (r = lease.take(L.bytes)) != PCPX_OK)
-            return r;
+        const float* d_points = call.upload(points, n * 3 * sizeof(float));
+        const float* d_normals = call.upload(gated ? opt_normals : nullptr, n * 3 * sizeof(float));
+        const u32* d_rows = call.upload(opt_rows, rows_count * sizeof(u32));
+        // the small outputs as one block: found, h, score, a pad, the two planes; and the inliers' rows
+        RansacSmall<4>* d = call.alloc<RansacSmall<4>>(sizeof(RansacSmall<4>));
+        u32* inl = opt_out_inliers ? call.alloc<u32>(capacity * sizeof(u32)) : nullptr;
+        char* base = call.scratch(L.bytes);
         // (a list of no rows is a set of no rows, not "all rows": the kernels tell the two apart by the pointer)
-        DevBuf stand_in(sh.pool);
-        if (opt_rows && !rows_count && (r = stand_in.alloc(sizeof(u32))) != PCPX_OK) return r;
-        const u32* d_rows = !opt_rows ? nullptr : rows_count ? in.rows.as<u32>() : stand_in.as<u32>();
-        const Cloud cloud{in.points.as<float>(), in.normals.as<float>(), d_rows, nullptr, static_cast<u32>(n), static_cast<u32>(capacity), params->origin_row};
-        Small* d = small.as<Small>();
-        const PlaneOut out{&d->found, &d->h, &d->score, inl.as<u32>(), nullptr, d->plane, refit ? d->refit : nullptr, nullptr, nullptr, nullptr};
-        if ((r = run_planes(L, static_cast<char*>(lease.p), cloud, *params, 0, out, s)) != PCPX_OK) return r;
-        PCPX_HIP(hipMemcpyAsync(&host, d, sizeof(Small), hipMemcpyDeviceToHost, s));
-        PCPX_HIP(hipStreamSynchronize(s));
-        if (opt_out_inliers && host.score) {
-            PCPX_HIP(hipMemcpyAsync(opt_out_inliers, inl.p, static_cast<size_t>(host.score) * sizeof(u32), hipMemcpyDeviceToHost, s));
-            PCPX_HIP(hipStreamSynchronize(s));
-        }
-        *out_found = host.found;
-        if (opt_out_hypothesis) *opt_out_hypothesis = host.h;
-        if (opt_out_score) *opt_out_score = host.score;
-        if (opt_out_plane) std::copy(host.plane, host.plane + 4, opt_out_plane);
-        if (refit) std::copy(host.refit, host.refit + 4, opt_out_refit);
-        return PCPX_OK;
+        if (opt_rows && !rows_count) d_rows = call.alloc<u32>(sizeof(u32));
+        int r;
+        if ((r = call.st) != PCPX_OK) return r;
+        const Cloud cloud{d_points, d_normals, d_rows, nullptr, static_cast<u32>(n), static_cast<u32>(capacity), params->origin_row};
+        const PlaneOut out{&d->found, &d->h, &d->score, inl, nullptr, d->model, refit ? d->refit : nullptr, nullptr, nullptr, nullptr};
+        if ((r = run_planes(L, base, cloud, *params, 0, out, call.s)) != PCPX_OK) return r;
+        return ransac_copy_out(call, d, inl, out_found, opt_out_hypothesis, opt_out_score, opt_out_inliers, opt_out_plane, refit ? opt_out_refit : nullptr);
     });
 }
 
@@ -870,15 +789,9 @@ int pcpx_plane_fit_dev(const float* d_points, uint64_t n, const uint32_t* d_opt_
     static const char* what = "pcpx_plane_fit_dev";
     int st = check_cloud(what, d_points, n, d_opt_rows, rows_capacity);
     if (st != PCPX_OK || (st = check_pfit(what, d_out_plane)) != PCPX_OK) return st;
-    if (device < 0 || device >= LEASE_MAX_DEVICES) return select_device(device);
-    return on_shared(device, what, [&](DeviceShared& sh) -> int {
-        const hipStream_t s = static_cast<hipStream_t>(stream);
+    return on_leased(device, what, stream, PFIT_SCRATCH_BYTES, [&](char* base, hipStream_t s) -> int {
         const FitRows set{d_points, d_opt_rows, d_opt_rows ? d_opt_rows_count : nullptr, static_cast<u32>(n), static_cast<u32>(rows_capacity), d_opt_rows != nullptr};
-        ScratchLease lease(sh, device, s);
-        int r;
-        if ((r = lease.take(PFIT_SCRATCH_BYTES)) != PCPX_OK) return r;
-        if ((r = pfit_device(set, static_cast<char*>(lease.p), nullptr, 0, nullptr, d_out_plane, d_opt_out_rms, s)) != PCPX_OK) return r;
-        return lease.leave_queued();
+        return pfit_device(set, base, nullptr, 0, nullptr, d_out_plane, d_opt_out_rms, s);
     });
 }
 
@@ -887,23 +800,17 @@ int pcpx_plane_fit(const float* points, uint64_t n, const uint32_t* opt_rows, ui
     static const char* what = "pcpx_plane_fit";
     int st = check_cloud(what, points, n, opt_rows, rows_count);
     if (st != PCPX_OK || (st = check_pfit(what, out_plane)) != PCPX_OK) return st;
-    if (device < 0 || device >= LEASE_MAX_DEVICES) return select_device(device);
-    return on_shared(device, what, [&](DeviceShared& sh) -> int {
-        PooledStream ps;
-        PCPX_HIP(pooled_stream_get(&ps.s));
-        const hipStream_t s = ps.s;
-        Staged in(sh.pool);
-        DevBuf out(sh.pool);
-        ScratchLease lease(sh, device, s);
+    return on_host_call(device, what, [&](HostCall& call) -> int {
         double host[5];
+        const float* d_points = call.upload(points, n * 3 * sizeof(float));
+        const u32* d_rows = call.upload(opt_rows, rows_count * sizeof(u32));
+        double* out = call.alloc<double>(sizeof(host));
+        char* base = call.scratch(PFIT_SCRATCH_BYTES);
+        const FitRows set{d_points, d_rows, nullptr, static_cast<u32>(n), static_cast<u32>(rows_count), opt_rows != nullptr};
         int r;
-        if ((r = in.upload(points, n, nullptr, opt_rows, rows_count, s)) != PCPX_OK || (r = out.alloc(sizeof(host))) != PCPX_OK ||
-            (r = lease.take(PFIT_SCRATCH_BYTES)) != PCPX_OK)
+        if ((r = call.st) != PCPX_OK || (r = pfit_device(set, base, nullptr, 0, nullptr, out, out + 4, call.s)) != PCPX_OK ||
+            (r = call.download(host, out, sizeof(host))) != PCPX_OK || (r = call.wait()) != PCPX_OK)
             return r;
-        const FitRows set{in.points.as<float>(), in.rows.as<u32>(), nullptr, static_cast<u32>(n), static_cast<u32>(rows_count), opt_rows != nullptr};
-        if ((r = pfit_device(set, static_cast<char*>(lease.p), nullptr, 0, nullptr, out.as<double>(), out.as<double>() + 4, s)) != PCPX_OK) return r;
-        PCPX_HIP(hipMemcpyAsync(host, out.p, sizeof(host), hipMemcpyDeviceToHost, s));
-        PCPX_HIP(hipStreamSynchronize(s));
         std::copy(host, host + 4, out_plane);
         if (opt_out_rms) *opt_out_rms = host[4];
         return PCPX_OK;
@@ -919,17 +826,11 @@ int pcpx_extract_planes_dev(const float* d_points, uint64_t n, const float* d_op
     if (st != PCPX_OK || (st = check_params(what, params, d_opt_normals, n)) != PCPX_OK ||
         (st = check_peel(what, params, n, d_out_labels, d_out_count, d_opt_out_refits)) != PCPX_OK)
         return st;
-    if (device < 0 || device >= LEASE_MAX_DEVICES) return select_device(device);
-    return on_shared(device, what, [&](DeviceShared& sh) -> int {
-        const hipStream_t s = static_cast<hipStream_t>(stream);
-        const Layout L(params->hypotheses, n, (params->flags & PCPX_PLANE_NORMALS) != 0, params->max_planes > 1);
+    const Layout L(params->hypotheses, n, (params->flags & PCPX_PLANE_NORMALS) != 0, params->max_planes > 1);
+    return on_leased(device, what, stream, L.bytes, [&](char* base, hipStream_t s) -> int {
         const Cloud in{d_points, gate_normals(params, d_opt_normals), nullptr, nullptr, static_cast<u32>(n), static_cast<u32>(n), 0u};
-        ScratchLease lease(sh, device, s);
-        int r;
-        if ((r = lease.take(L.bytes)) != PCPX_OK) return r;
         const PlaneOut out{nullptr, nullptr, nullptr, nullptr, nullptr, d_opt_out_planes, d_opt_out_refits, d_out_labels, d_out_count, d_opt_out_scores};
-        if ((r = run_planes(L, static_cast<char*>(lease.p), in, *params, params->max_planes, out, s)) != PCPX_OK) return r;
-        return lease.leave_queued();
+        return run_planes(L, base, in, *params, params->max_planes, out, s);
     });
 }
 
@@ -941,34 +842,29 @@ int pcpx_extract_planes(const float* points, uint64_t n, const float* opt_normal
     if (st != PCPX_OK || (st = check_params(what, params, opt_normals, n)) != PCPX_OK ||
         (st = check_peel(what, params, n, out_labels, out_count, opt_out_refits)) != PCPX_OK)
         return st;
-    if (device < 0 || device >= LEASE_MAX_DEVICES) return select_device(device);
-    return on_shared(device, what, [&](DeviceShared& sh) -> int {
-        PooledStream ps;
-        PCPX_HIP(pooled_stream_get(&ps.s));
-        const hipStream_t s = ps.s;
+    return on_host_call(device, what, [&](HostCall& call) -> int {
         const bool gated = (params->flags & PCPX_PLANE_NORMALS) != 0, refit = (params->flags & PCPX_PLANE_REFIT) != 0;
         const u32 rounds = params->max_planes;
         const Layout L(params->hypotheses, n, gated, rounds > 1);
-        Staged in(sh.pool);
-        DevBuf labels(sh.pool), small(sh.pool);
-        ScratchLease lease(sh, device, s);
         // the small outputs as one block: planes, refits, scores, the count
         const size_t planes_at = 0, refits_at = static_cast<size_t>(rounds) * 4 * sizeof(double), scores_at = 2 * refits_at,
                      count_at = scores_at + static_cast<size_t>(rounds) * sizeof(u32), small_bytes = count_at + sizeof(u32);
+        const float* d_points = call.upload(points, n * 3 * sizeof(float));
+        const float* d_normals = call.upload(gated ? opt_normals : nullptr, n * 3 * sizeof(float));
+        char* d = call.alloc<char>(small_bytes);
+        u32* labels = call.alloc<u32>(n * sizeof(u32));
+        char* base = call.scratch(L.bytes);
         int r;
-        if ((r = in.upload(points, n, gated ? opt_normals : nullptr, nullptr, 0, s)) != PCPX_OK || (r = small.alloc(small_bytes)) != PCPX_OK ||
-            (n && (r = labels.alloc(n * sizeof(u32))) != PCPX_OK) || (r = lease.take(L.bytes)) != PCPX_OK)
-            return r;
-        char* d = small.as<char>();
-        const Cloud cloud{in.points.as<float>(), in.normals.as<float>(), nullptr, nullptr, static_cast<u32>(n), static_cast<u32>(n), 0u};
+        if ((r = call.st) != PCPX_OK) return r;
+        const Cloud cloud{d_points, d_normals, nullptr, nullptr, static_cast<u32>(n), static_cast<u32>(n), 0u};
         const PlaneOut out{nullptr, nullptr, nullptr, nullptr, nullptr, reinterpret_cast<double*>(d + planes_at),
-                           refit ? reinterpret_cast<double*>(d + refits_at) : nullptr, labels.as<u32>(), reinterpret_cast<u32*>(d + count_at),
+                           refit ? reinterpret_cast<double*>(d + refits_at) : nullptr, labels, reinterpret_cast<u32*>(d + count_at),
                            reinterpret_cast<u32*>(d + scores_at)};
-        if ((r = run_planes(L, static_cast<char*>(lease.p), cloud, *params, rounds, out, s)) != PCPX_OK) return r;
+        if ((r = run_planes(L, base, cloud, *params, rounds, out, call.s)) != PCPX_OK) return r;
         std::vector<char> host(small_bytes);
-        PCPX_HIP(hipMemcpyAsync(host.data(), d, small_bytes, hipMemcpyDeviceToHost, s));
-        if (n) PCPX_HIP(hipMemcpyAsync(out_labels, labels.p, n * sizeof(u32), hipMemcpyDeviceToHost, s));
-        PCPX_HIP(hipStreamSynchronize(s));
+        if ((r = call.download(host.data(), d, small_bytes)) != PCPX_OK || (n && (r = call.download(out_labels, labels, n * sizeof(u32))) != PCPX_OK) ||
+            (r = call.wait()) != PCPX_OK)
+            return r;
         std::memcpy(out_count, host.data() + count_at, sizeof(u32));
         if (opt_out_planes) std::memcpy(opt_out_planes, host.data() + planes_at, refits_at);
         if (refit) std::memcpy(opt_out_refits, host.data() + refits_at, refits_at);

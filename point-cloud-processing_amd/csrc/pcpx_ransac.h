@@ -1,11 +1,15 @@
 // pcpx_ransac.h -- what the hypothesis-and-score entry points share (pcpx_register.hip: rigid poses, DESIGN.md section 24;
-// pcpx_planes.hip: planes, section 26): the count word of an invalid hypothesis, the best-key reduction over the counts, the
-// compaction of flagged records, and the fixed order of the float64 sums of their least-squares fits.  Included by .hip translation
-// units only.
+// pcpx_planes.hip: planes, section 26): the plan that cuts the records into segments, the count word of an invalid hypothesis, the
+// best-key reduction over the counts, the compaction of flagged records, the scratch of their least-squares fits (whose float64 sums
+// are pcpx_fixed_sum.h's) and the copy-out of a host-form call.  Included by .hip translation units only.
 #ifndef PCPX_RANSAC_H
 #define PCPX_RANSAC_H
 
 #include "pcpx_device.h"
+#include "pcpx_fixed_sum.h"
+#include "pcpx_lease.h"
+
+#include <algorithm>
 
 namespace pcpx {
 namespace {
@@ -13,12 +17,35 @@ namespace {
 constexpr u32 RG_BLOCK = 256;  // threads of the row-wise kernels
 constexpr u32 RG_BEST_PER_THREAD = 16;  // hypotheses of a k_ransac_best thread
 constexpr u32 RG_INVALID = 0xFFFFFFFFu;  // the count word of an invalid hypothesis (a count is at most C < 2^32 - 1)
-// the fit: FIT_BLOCKS blocks of RG_BLOCK threads stride over the pairs; a block leaves FIT_TERMS doubles
-constexpr u32 FIT_BLOCKS = 64;
-constexpr u32 FIT_TERMS = 16;
+constexpr u32 FIT_TERMS = 16;  // the doubles a block's partial sums of a fit are apart (pcpx_fixed_sum.h)
+// the scratch of a fit whose state is `state` doubles: the blocks' partial sums, then the state
+constexpr size_t fit_bytes(u32 state) { return (static_cast<size_t>(FIT_BLOCKS) * FIT_TERMS + state) * sizeof(double); }
 
 inline u32 blocks_of(u64 n, u32 per) { return static_cast<u32>((n + per - 1) / per); }
-inline size_t padded(u64 bytes) { return (bytes + 255) / 256 * 256; }
+
+// The plan: a wave is 64 hypotheses on one segment of the records, a call should be several rounds of what the device holds
+// (PLAN_TARGET_WAVES), a segment is never shorter than PLAN_MIN_SEGMENT_ROWS (a wave's prologue -- three gathers and what it makes
+// of them -- is paid per segment) and there are never more than PLAN_MAX_SEGMENTS (the best-key reduction reads a word per
+// hypothesis and segment).
+constexpr u64 PLAN_TARGET_WAVES = 16384;
+constexpr u64 PLAN_MAX_SEGMENTS = 256;
+constexpr u64 PLAN_MIN_SEGMENT_ROWS = 256;
+constexpr u64 PLAN_LAUNCH_HYPOTHESES = 1ull << 30;  // hypotheses of one launch (a grid's thread count stays below 2^32)
+struct SegmentPlan {
+    u32 segments = 0;
+    u64 rows = 0;  // per segment
+};
+inline SegmentPlan segment_plan(u64 hypotheses, u64 capacity)
+{
+    SegmentPlan p;
+    if (!capacity) return p;
+    const u64 groups = std::max<u64>(1, (hypotheses + GROUP - 1) / GROUP);
+    const u64 want = (PLAN_TARGET_WAVES + groups - 1) / groups;
+    const u64 s0 = std::max<u64>(1, std::min({want, PLAN_MAX_SEGMENTS, capacity / PLAN_MIN_SEGMENT_ROWS}));
+    p.rows = ((capacity + s0 - 1) / s0 + PLAN_MIN_SEGMENT_ROWS - 1) / PLAN_MIN_SEGMENT_ROWS * PLAN_MIN_SEGMENT_ROWS;
+    p.segments = static_cast<u32>((capacity + p.rows - 1) / p.rows);
+    return p;
+}
 
 // RG_BEST_PER_THREAD hypotheses per thread, a block's threads side by side in each round: the sum of a hypothesis's segment counts
 // (integers: exact, and independent of the split), the key ((count + 1) << 32 | (0xFFFFFFFF - h)) of a valid one -- larger count
@@ -59,32 +86,29 @@ __global__ __launch_bounds__(RG_BLOCK) void k_reg_compact(u32 capacity, const ui
     if (k < capacity && flag[k]) positions[place[k]] = k;
 }
 
-// The order of a fit's float64 sums.  A thread has added its items in ascending order (a stride of the grid apart) into acc; the
-// block's threads are added by a fixed tree, and the block leaves its sums in partial[block * FIT_TERMS + term].  Every thread of
-// the block calls this.
-template <int NT>
-__device__ __forceinline__ void fit_block_sums(const double (&acc)[NT], double* __restrict__ partial)
+// The small outputs of a host-form RANSAC call as one block on the device (the model is the transform's 16 doubles or the plane's 4),
+// and their way back: the block after one wait, then the `score` inlier positions after a second one, only where there are some.
+template <int DOUBLES>
+struct RansacSmall {
+    u32 found, h, score, pad;
+    double model[DOUBLES], refit[DOUBLES];
+};
+template <int DOUBLES>
+int ransac_copy_out(HostCall& call, const RansacSmall<DOUBLES>* d, const u32* d_inliers, u32* out_found, u32* opt_out_hypothesis, u32* opt_out_score,
+                    u32* opt_out_inliers, double* opt_out_model, double* opt_out_refit)
 {
-    __shared__ double tree[RG_BLOCK];
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
-        tree[threadIdx.x] = acc[i];
-        __syncthreads();
-        for (u32 off = RG_BLOCK / 2; off > 0; off >>= 1) {
-            if (threadIdx.x < off) tree[threadIdx.x] += tree[threadIdx.x + off];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) partial[blockIdx.x * FIT_TERMS + i] = tree[0];
-        __syncthreads();
+    RansacSmall<DOUBLES> host;
+    int st;
+    if ((st = call.download(&host, d, sizeof(host))) != PCPX_OK || (st = call.wait()) != PCPX_OK) return st;
+    if (opt_out_inliers && host.score) {
+        if ((st = call.download(opt_out_inliers, d_inliers, static_cast<size_t>(host.score) * sizeof(u32))) != PCPX_OK || (st = call.wait()) != PCPX_OK) return st;
     }
-}
-// ... and the blocks' partial sums of one term in block order
-__device__ __forceinline__ double fit_sum_blocks(const double* __restrict__ partial, u32 nblocks, u32 term)
-{
-    double sum = 0.0;
-#pragma unroll 16
-    for (u32 b = 0; b < nblocks; ++b) sum += partial[b * FIT_TERMS + term];  // (in block order; the loads of a batch are issued together)
-    return sum;
+    *out_found = host.found;
+    if (opt_out_hypothesis) *opt_out_hypothesis = host.h;
+    if (opt_out_score) *opt_out_score = host.score;
+    if (opt_out_model) std::copy(host.model, host.model + DOUBLES, opt_out_model);
+    if (opt_out_refit) std::copy(host.refit, host.refit + DOUBLES, opt_out_refit);
+    return PCPX_OK;
 }
 
 }  // namespace

@@ -7,7 +7,8 @@
 //   k_ransac_best    one thread per hypothesis over its segments' counts; the best key by a wave reduction and one atomicMax
 //   k_ransac_emit    the winner rebuilt by the same device function: its transform, and the inlier flag of every record;
 //                    pcpx_scan.h and k_reg_compact write the inliers' positions
-//   k_fit_partial / k_fit_final / k_fit_solve   the float64 sums of the rigid fit in a fixed order, and Horn's closed form
+//   k_fixed_partial / k_fixed_final (pcpx_fixed_sum.h) over RigidSum<1..3>, k_fit_solve   the float64 sums of the rigid fit in the
+//                    fixed order, and Horn's closed form
 #include "pcpx_device.h"
 #include "pcpx_horn.h"
 #include "pcpx_lease.h"
@@ -24,16 +25,11 @@ namespace {
 
 constexpr u32 RG_WAVES = 4;    // waves of a k_ransac_count block: four consecutive hypothesis groups on one segment (they share its records in the scalar cache)
 constexpr u32 RG_UNROLL = 4;   // records of one trip of k_ransac_count's loop
-// The plan, by the reasoning of pcpx_match.hip's: a wave is 64 hypotheses on one segment, a call should be several rounds of what
-// the device holds, a segment is never shorter than RG_MIN_SEGMENT_ROWS (a wave's prologue -- three gathers and the two frames --
-// is paid per segment) and there are never more than RG_MAX_SEGMENTS (k_ransac_best reads a word per hypothesis and segment).
-constexpr u64 RG_TARGET_WAVES = 16384;
-constexpr u64 RG_MAX_SEGMENTS = 256;
-constexpr u64 RG_MIN_SEGMENT_ROWS = 256;
-constexpr u64 RG_LAUNCH_HYPOTHESES = 1ull << 30;  // hypotheses of one launch (a grid's thread count stays below 2^32)
+// (the plan -- segment_plan and its constants --: pcpx_ransac.h)
 // the doubles of the fit's state: [0] the number of usable pairs, [1..3] sum p, [4..6] sum q, [8..10] pbar, [11..13] qbar,
 // [16..24] H, [32] sum of squared residuals, [40..55] the transform
 constexpr u32 FIT_STATE = 64, FS_N = 0, FS_SUM = 1, FS_PBAR = 8, FS_QBAR = 11, FS_H = 16, FS_SS = 32, FS_XF = 40;
+constexpr size_t FIT_SCRATCH_BYTES = fit_bytes(FIT_STATE);
 
 
 struct Rec {
@@ -43,38 +39,24 @@ static_assert(sizeof(Rec) == 32, "one x8 scalar load");
 
 // Where everything lies in the scratch of a RANSAC call (byte offsets, each a multiple of 256), from the capacity and T alone.
 struct Layout {
-    u32 segments = 0;
-    u64 rows = 0;  // per segment
+    SegmentPlan plan;
     size_t rec = 0, counts = 0, key = 0, flag = 0, place = 0, sums = 0, positions = 0, npos = 0, xf = 0, fit = 0, bytes = 0;
-    Layout(u64 hypotheses, u64 capacity)
+    Layout(u64 hypotheses, u64 capacity) : plan(segment_plan(hypotheses, capacity))
     {
-        if (capacity) {
-            const u64 groups = std::max<u64>(1, (hypotheses + GROUP - 1) / GROUP);
-            const u64 want = (RG_TARGET_WAVES + groups - 1) / groups;
-            const u64 s0 = std::max<u64>(1, std::min({want, RG_MAX_SEGMENTS, capacity / RG_MIN_SEGMENT_ROWS}));
-            rows = ((capacity + s0 - 1) / s0 + RG_MIN_SEGMENT_ROWS - 1) / RG_MIN_SEGMENT_ROWS * RG_MIN_SEGMENT_ROWS;
-            segments = static_cast<u32>((capacity + rows - 1) / rows);
-        }
-        size_t at = 0;
-        auto take = [&](u64 b) {
-            const size_t here = at;
-            at += padded(b);
-            return here;
-        };
-        rec = take(capacity * sizeof(Rec));
-        counts = take(hypotheses * segments * sizeof(u32));
-        key = take(sizeof(u64));
-        flag = take(capacity);
-        place = take(capacity * sizeof(u32));
-        sums = take(static_cast<u64>(scan_tiles(capacity)) * sizeof(u32));
-        positions = take(capacity * sizeof(u32));
-        npos = take(sizeof(u64));
-        xf = take(16 * sizeof(double));
-        fit = take((static_cast<u64>(FIT_BLOCKS) * FIT_TERMS + FIT_STATE) * sizeof(double));
-        bytes = at;
+        Carve c;
+        rec = c.take(capacity * sizeof(Rec));
+        counts = c.take(hypotheses * plan.segments * sizeof(u32));
+        key = c.take(sizeof(u64));
+        flag = c.take(capacity);
+        place = c.take(capacity * sizeof(u32));
+        sums = c.take(static_cast<u64>(scan_tiles(capacity)) * sizeof(u32));
+        positions = c.take(capacity * sizeof(u32));
+        npos = c.take(sizeof(u64));
+        xf = c.take(16 * sizeof(double));
+        fit = c.take(FIT_SCRATCH_BYTES);
+        bytes = c.bytes();
     }
 };
-constexpr size_t FIT_SCRATCH_BYTES = (static_cast<size_t>(FIT_BLOCKS) * FIT_TERMS + FIT_STATE) * sizeof(double);
 
 // the two clouds and the correspondences of a call, as the kernels see them
 struct Pairs {
@@ -83,12 +65,7 @@ struct Pairs {
     const u32* pairs;
     const u64* d_count;  // null: capacity
     u32 np, nq, capacity;
-    __device__ __forceinline__ u32 count() const
-    {
-        if (!d_count) return capacity;
-        const u64 c = *d_count;
-        return c < capacity ? static_cast<u32>(c) : capacity;
-    }
+    __device__ __forceinline__ u32 count() const { return clamped_count(d_count, capacity); }
     // the six coordinates of correspondence k (k below the capacity); false when it is not usable
     __device__ __forceinline__ bool load(u32 k, float (&x)[6]) const
     {
@@ -317,13 +294,7 @@ struct FitSet {
     const u32* positions;    // (may be null when listed with room for none)
     const u64* d_positions;  // null: positions_capacity
     u32 positions_capacity;
-    __device__ __forceinline__ u32 items(u32 C) const
-    {
-        if (!listed) return C;
-        if (!d_positions) return positions_capacity;
-        const u64 c = *d_positions;
-        return c < positions_capacity ? static_cast<u32>(c) : positions_capacity;
-    }
+    __device__ __forceinline__ u32 items(u32 C) const { return listed ? clamped_count(d_positions, positions_capacity) : C; }
     __device__ __forceinline__ bool load(u32 C, u32 j, double (&x)[6]) const
     {
         const u32 k = listed ? positions[j] : j;
@@ -335,22 +306,26 @@ struct FitSet {
     }
 };
 
-constexpr int fit_terms(int pass) { return pass == 1 ? 7 : pass == 2 ? 9 : 1; }
-
-// Pass 1: the number of usable pairs and the sums of their points.  Pass 2: H about the centroids.  Pass 3: the squared residuals
-// under the transform.  A thread adds its pairs in ascending order (a stride of the grid apart), the block's threads are added by a
-// fixed tree, and the block leaves its sums in partial[block * FIT_TERMS + term].
+// The three sums of the fit, in pcpx_fixed_sum.h's order.  Pass 1: the number of usable pairs and the sums of their points, and from
+// them the centroids.  Pass 2: H about the centroids.  Pass 3: the squared residuals under the transform, and from them the root
+// mean square (NaN with fewer than three usable pairs).
 template <int PASS>
-__global__ __launch_bounds__(RG_BLOCK) void k_fit_partial(FitSet set, const double* __restrict__ state, double* __restrict__ partial)
-{
-    constexpr int NT = fit_terms(PASS);
-    const u32 C = set.in.count(), n = set.items(C);
-    double acc[NT];
-#pragma unroll
-    for (int i = 0; i < NT; ++i) acc[i] = 0.0;
-    for (u64 j = static_cast<u64>(blockIdx.x) * RG_BLOCK + threadIdx.x; j < n; j += static_cast<u64>(gridDim.x) * RG_BLOCK) {
+struct RigidSum {
+    static constexpr int TERMS = PASS == 1 ? 7 : PASS == 2 ? 9 : 1, STRIDE = FIT_TERMS;
+    FitSet set;
+    double* state;
+    double* out_rms;  // (pass 3)
+    u32 C;            // (items() leaves the number of correspondences here for add())
+    __device__ __forceinline__ bool live() const { return true; }
+    __device__ __forceinline__ u32 items()
+    {
+        C = set.in.count();
+        return set.items(C);
+    }
+    __device__ __forceinline__ void add(u32 j, double (&acc)[TERMS]) const
+    {
         double x[6];
-        if (!set.load(C, static_cast<u32>(j), x)) continue;
+        if (!set.load(C, j, x)) return;
         if constexpr (PASS == 1) {
             acc[0] += 1.0;
 #pragma unroll
@@ -370,30 +345,26 @@ __global__ __launch_bounds__(RG_BLOCK) void k_fit_partial(FitSet set, const doub
             }
         }
     }
-    fit_block_sums<NT>(acc, partial);  // (pcpx_ransac.h: the fixed tree)
-}
-
-// One block: thread `term` adds the blocks' partial sums of its term in block order.  Pass 1 also leaves the centroids; pass 3 the
-// root mean square (NaN with fewer than three usable pairs).
-template <int PASS>
-__global__ __launch_bounds__(64) void k_fit_final(const double* __restrict__ partial, u32 nblocks, double* __restrict__ state, double* __restrict__ out_rms)
-{
-    constexpr int NT = fit_terms(PASS);
-    if (threadIdx.x >= NT) return;
-    const double sum = fit_sum_blocks(partial, nblocks, threadIdx.x);  // (pcpx_ransac.h: in block order)
-    if constexpr (PASS == 1) {
-        const double n = __shfl(sum, 0);
-        state[FS_N + threadIdx.x] = sum;  // (FS_SUM = FS_N + 1)
-        if (threadIdx.x >= 1) state[FS_PBAR + threadIdx.x - 1] = n > 0.0 ? sum / n : 0.0;  // (FS_QBAR = FS_PBAR + 3)
-    } else if constexpr (PASS == 2) {
-        state[FS_H + threadIdx.x] = sum;
-    } else {
-        const double n = state[FS_N];
-        state[FS_SS] = sum;
-        *out_rms = n >= 3.0 ? std::sqrt(sum / n) : std::numeric_limits<double>::quiet_NaN();
+    __device__ __forceinline__ void finish(u32 term, double sum) const
+    {
+        if constexpr (PASS == 1) {
+            const double n = __shfl(sum, 0);
+            state[FS_N + term] = sum;  // (FS_SUM = FS_N + 1)
+            if (term >= 1) state[FS_PBAR + term - 1] = n > 0.0 ? sum / n : 0.0;  // (FS_QBAR = FS_PBAR + 3)
+        } else if constexpr (PASS == 2) {
+            state[FS_H + term] = sum;
+        } else {
+            const double n = state[FS_N];
+            state[FS_SS] = sum;
+            *out_rms = n >= 3.0 ? std::sqrt(sum / n) : std::numeric_limits<double>::quiet_NaN();
+        }
     }
-}
-static_assert(FS_SUM == FS_N + 1 && FS_QBAR == FS_PBAR + 3, "k_fit_final<1> writes them as one run");
+};
+static_assert(FS_SUM == FS_N + 1 && FS_QBAR == FS_PBAR + 3, "pass 1 writes them as one run");
+// (named, not RigidSum<1>: a kernel then reads k_fixed_partial<RigidCentroids> in a profile)
+struct RigidCentroids : RigidSum<1> {};
+struct RigidCross : RigidSum<2> {};
+struct RigidResiduals : RigidSum<3> {};
 
 // One thread: Horn's closed form on H, t = qbar - R pbar.  With fewer than three usable pairs: `fallback` (16 doubles) or the identity.
 __global__ __launch_bounds__(64) void k_fit_solve(double* __restrict__ state, const double* __restrict__ fallback, double* __restrict__ out)
@@ -423,22 +394,15 @@ __global__ __launch_bounds__(64) void k_fit_solve(double* __restrict__ state, co
     }
 }
 
-// The fit, enqueued on s.  scratch: FIT_SCRATCH_BYTES.  The grid is always FIT_BLOCKS blocks, so the order of the sums -- and with it
-// every bit of the result -- depends on the pairs alone, not on the capacities of the call.
+// The fit, enqueued on s.  scratch: FIT_SCRATCH_BYTES.
 int fit_device(const FitSet& set, char* scratch, const double* d_fallback, double* d_out, double* d_out_rms, hipStream_t s)
 {
     double* partial = reinterpret_cast<double*>(scratch);
     double* state = partial + static_cast<size_t>(FIT_BLOCKS) * FIT_TERMS;
-    const u32 blocks = FIT_BLOCKS;
-    k_fit_partial<1><<<blocks, RG_BLOCK, 0, s>>>(set, state, partial);
-    k_fit_final<1><<<1, 64, 0, s>>>(partial, blocks, state, nullptr);
-    k_fit_partial<2><<<blocks, RG_BLOCK, 0, s>>>(set, state, partial);
-    k_fit_final<2><<<1, 64, 0, s>>>(partial, blocks, state, nullptr);
+    fixed_sum(RigidCentroids{{set, state, nullptr, 0u}}, partial, s);
+    fixed_sum(RigidCross{{set, state, nullptr, 0u}}, partial, s);
     k_fit_solve<<<1, 64, 0, s>>>(state, d_fallback, d_out);
-    if (d_out_rms) {
-        k_fit_partial<3><<<blocks, RG_BLOCK, 0, s>>>(set, state, partial);
-        k_fit_final<3><<<1, 64, 0, s>>>(partial, blocks, state, d_out_rms);
-    }
+    if (d_out_rms) fixed_sum(RigidResiduals{{set, state, d_out_rms, 0u}}, partial, s);
     PCPX_HIP(hipGetLastError());
     return PCPX_OK;
 }
@@ -471,11 +435,11 @@ int ransac_device(const Layout& L, char* base, const Pairs& in, const RansacArgs
     PCPX_HIP(hipMemsetAsync(key, 0, sizeof(u64), s));
     if (in.capacity) {
         k_reg_pack<<<blocks_of(in.capacity, RG_BLOCK), RG_BLOCK, 0, s>>>(in, rec);
-        for (u64 h0 = 0; h0 < T; h0 += RG_LAUNCH_HYPOTHESES) {
-            const u64 here = std::min(RG_LAUNCH_HYPOTHESES, T - h0);
-            const dim3 grid(blocks_of((here + GROUP - 1) / GROUP, RG_WAVES), L.segments);
-            k_ransac_count<<<grid, 64 * RG_WAVES, 0, s>>>(rec, in.capacity, in.d_count, h0, T, a.seed, a.s2, a.tau2, L.rows, counts);
-            k_ransac_best<<<blocks_of(here, RG_BLOCK * RG_BEST_PER_THREAD), RG_BLOCK, 0, s>>>(counts, h0, h0 + here, T, L.segments, key);
+        for (u64 h0 = 0; h0 < T; h0 += PLAN_LAUNCH_HYPOTHESES) {
+            const u64 here = std::min(PLAN_LAUNCH_HYPOTHESES, T - h0);
+            const dim3 grid(blocks_of((here + GROUP - 1) / GROUP, RG_WAVES), L.plan.segments);
+            k_ransac_count<<<grid, 64 * RG_WAVES, 0, s>>>(rec, in.capacity, in.d_count, h0, T, a.seed, a.s2, a.tau2, L.plan.rows, counts);
+            k_ransac_best<<<blocks_of(here, RG_BLOCK * RG_BEST_PER_THREAD), RG_BLOCK, 0, s>>>(counts, h0, h0 + here, T, L.plan.segments, key);
         }
     } else {
         PCPX_HIP(hipMemsetAsync(npos, 0, sizeof(u64), s));  // (a scan of nothing writes no total)
@@ -553,24 +517,14 @@ int check_fit(const char* what, const void* positions, u64 positions_capacity, c
     return PCPX_OK;
 }
 
-// the clouds and correspondences of a host-form call on the device
-struct Staged {
-    DevBuf p, q, pairs;
-    explicit Staged(DevPool& pool) : p(pool), q(pool), pairs(pool) {}
-    int upload(const float* h_p, u64 np, const float* h_q, u64 nq, const u32* h_pairs, u64 count, hipStream_t s)
-    {
-        int st;
-        if (np && ((st = p.alloc(np * 3 * sizeof(float))) != PCPX_OK || (st = upload_pageable(p.p, h_p, np * 3 * sizeof(float), s)) != PCPX_OK)) return st;
-        if (nq && ((st = q.alloc(nq * 3 * sizeof(float))) != PCPX_OK || (st = upload_pageable(q.p, h_q, nq * 3 * sizeof(float), s)) != PCPX_OK)) return st;
-        if (count && ((st = pairs.alloc(count * 2 * sizeof(u32))) != PCPX_OK || (st = upload_pageable(pairs.p, h_pairs, count * 2 * sizeof(u32), s)) != PCPX_OK))
-            return st;
-        return PCPX_OK;
-    }
-    Pairs view(u64 np, u64 nq, u64 count) const
-    {
-        return Pairs{p.as<float>(), q.as<float>(), pairs.as<u32>(), nullptr, static_cast<u32>(np), static_cast<u32>(nq), static_cast<u32>(count)};
-    }
-};
+// the clouds and the correspondences of a host-form call on the device, uploaded in this order
+Pairs staged_pairs(HostCall& call, const float* p, u64 np, const float* q, u64 nq, const u32* pairs, u64 count)
+{
+    const float* d_p = call.upload(p, np * 3 * sizeof(float));
+    const float* d_q = call.upload(q, nq * 3 * sizeof(float));
+    const u32* d_pairs = call.upload(pairs, count * 2 * sizeof(u32));
+    return Pairs{d_p, d_q, d_pairs, nullptr, static_cast<u32>(np), static_cast<u32>(nq), static_cast<u32>(count)};
+}
 
 }  // namespace
 
@@ -596,8 +550,8 @@ int pcpx_ransac_plan(uint64_t hypotheses, uint64_t pairs_capacity, uint32_t* out
         int st = check_clouds(what, nullptr, 0, nullptr, 0, &pairs_capacity, pairs_capacity);  // (the sizes; there are no arrays)
         if (st != PCPX_OK || (st = check_ransac(what, hypotheses, 0.f, 0.f, 0, &hypotheses, nullptr)) != PCPX_OK) return st;
         const Layout L(hypotheses, pairs_capacity);
-        if (out_segments) *out_segments = L.segments;
-        if (out_segment_rows) *out_segment_rows = L.rows;
+        if (out_segments) *out_segments = L.plan.segments;
+        if (out_segment_rows) *out_segment_rows = L.plan.rows;
         if (out_scratch_bytes) *out_scratch_bytes = L.bytes;
         return PCPX_OK;
     });
@@ -612,20 +566,13 @@ int pcpx_ransac_rigid_dev(const float* d_p, uint64_t np, const float* d_q, uint6
     static const char* what = "pcpx_ransac_rigid_dev";
     int st = check_clouds(what, d_p, np, d_q, nq, d_pairs, pairs_capacity);
     if (st != PCPX_OK || (st = check_ransac(what, hypotheses, max_distance_sq, edge_similarity_sq, flags, d_out_found, d_opt_out_refit)) != PCPX_OK) return st;
-    if (device < 0 || device >= LEASE_MAX_DEVICES) return select_device(device);
-    return on_shared(device, what, [&](DeviceShared& sh) -> int {
-        const hipStream_t s = static_cast<hipStream_t>(stream);
-        const Layout L(hypotheses, pairs_capacity);
+    const Layout L(hypotheses, pairs_capacity);
+    return on_leased(device, what, stream, L.bytes, [&](char* base, hipStream_t s) -> int {
         const Pairs in{d_p, d_q, d_pairs, d_opt_count, static_cast<u32>(np), static_cast<u32>(nq), static_cast<u32>(pairs_capacity)};
-        ScratchLease lease(sh, device, s);
-        int r;
-        if ((r = lease.take(L.bytes)) != PCPX_OK) return r;
-        if ((r = ransac_device(L, static_cast<char*>(lease.p), in, RansacArgs{hypotheses, seed, max_distance_sq, edge_similarity_sq, flags},
-                               RansacOut{d_out_found, d_opt_out_hypothesis, d_opt_out_score, d_opt_out_inliers, d_opt_out_inlier_count, d_opt_out_transform,
-                                         d_opt_out_refit},
-                               s)) != PCPX_OK)
-            return r;
-        return lease.leave_queued();
+        return ransac_device(L, base, in, RansacArgs{hypotheses, seed, max_distance_sq, edge_similarity_sq, flags},
+                             RansacOut{d_out_found, d_opt_out_hypothesis, d_opt_out_score, d_opt_out_inliers, d_opt_out_inlier_count, d_opt_out_transform,
+                                       d_opt_out_refit},
+                             s);
     });
 }
 
@@ -637,41 +584,20 @@ int pcpx_ransac_rigid(const float* p, uint64_t np, const float* q, uint64_t nq, 
     static const char* what = "pcpx_ransac_rigid";
     int st = check_clouds(what, p, np, q, nq, pairs, count);
     if (st != PCPX_OK || (st = check_ransac(what, hypotheses, max_distance_sq, edge_similarity_sq, flags, out_found, opt_out_refit)) != PCPX_OK) return st;
-    if (device < 0 || device >= LEASE_MAX_DEVICES) return select_device(device);
-    return on_shared(device, what, [&](DeviceShared& sh) -> int {
-        PooledStream ps;
-        PCPX_HIP(pooled_stream_get(&ps.s));
-        const hipStream_t s = ps.s;
+    return on_host_call(device, what, [&](HostCall& call) -> int {
+        const bool refit = (flags & PCPX_RANSAC_REFIT) != 0;
         const Layout L(hypotheses, count);
-        Staged in(sh.pool);
+        const Pairs in = staged_pairs(call, p, np, q, nq, pairs, count);
         // the small outputs as one block: found, h, score, a pad, the two transforms; and the positions
-        DevBuf small(sh.pool), pos(sh.pool);
-        ScratchLease lease(sh, device, s);
-        struct Small {
-            u32 found, h, score, pad;
-            double xf[16], refit[16];
-        } host;
+        RansacSmall<16>* d = call.alloc<RansacSmall<16>>(sizeof(RansacSmall<16>));
+        u32* pos = opt_out_inliers ? call.alloc<u32>(count * sizeof(u32)) : nullptr;
+        char* base = call.scratch(L.bytes);
         int r;
-        if ((r = in.upload(p, np, q, nq, pairs, count, s)) != PCPX_OK || (r = small.alloc(sizeof(Small))) != PCPX_OK ||
-            (opt_out_inliers && count && (r = pos.alloc(count * sizeof(u32))) != PCPX_OK) || (r = lease.take(L.bytes)) != PCPX_OK)
+        if ((r = call.st) != PCPX_OK ||
+            (r = ransac_device(L, base, in, RansacArgs{hypotheses, seed, max_distance_sq, edge_similarity_sq, flags},
+                               RansacOut{&d->found, &d->h, &d->score, pos, nullptr, d->model, refit ? d->refit : nullptr}, call.s)) != PCPX_OK)
             return r;
-        Small* d = small.as<Small>();
-        if ((r = ransac_device(L, static_cast<char*>(lease.p), in.view(np, nq, count), RansacArgs{hypotheses, seed, max_distance_sq, edge_similarity_sq, flags},
-                               RansacOut{&d->found, &d->h, &d->score, pos.as<u32>(), nullptr, d->xf, (flags & PCPX_RANSAC_REFIT) ? d->refit : nullptr}, s)) !=
-            PCPX_OK)
-            return r;
-        PCPX_HIP(hipMemcpyAsync(&host, d, sizeof(Small), hipMemcpyDeviceToHost, s));
-        PCPX_HIP(hipStreamSynchronize(s));
-        if (opt_out_inliers && host.score) {
-            PCPX_HIP(hipMemcpyAsync(opt_out_inliers, pos.p, static_cast<size_t>(host.score) * sizeof(u32), hipMemcpyDeviceToHost, s));
-            PCPX_HIP(hipStreamSynchronize(s));
-        }
-        *out_found = host.found;
-        if (opt_out_hypothesis) *opt_out_hypothesis = host.h;
-        if (opt_out_score) *opt_out_score = host.score;
-        if (opt_out_transform) std::copy(host.xf, host.xf + 16, opt_out_transform);
-        if (flags & PCPX_RANSAC_REFIT) std::copy(host.refit, host.refit + 16, opt_out_refit);
-        return PCPX_OK;
+        return ransac_copy_out(call, d, pos, out_found, opt_out_hypothesis, opt_out_score, opt_out_inliers, opt_out_transform, refit ? opt_out_refit : nullptr);
     });
 }
 
@@ -682,17 +608,10 @@ int pcpx_rigid_fit_dev(const float* d_p, uint64_t np, const float* d_q, uint64_t
     static const char* what = "pcpx_rigid_fit_dev";
     int st = check_clouds(what, d_p, np, d_q, nq, d_pairs, pairs_capacity);
     if (st != PCPX_OK || (st = check_fit(what, d_opt_positions, positions_capacity, d_out_transform)) != PCPX_OK) return st;
-    if (device < 0 || device >= LEASE_MAX_DEVICES) return select_device(device);
-    return on_shared(device, what, [&](DeviceShared& sh) -> int {
-        const hipStream_t s = static_cast<hipStream_t>(stream);
+    return on_leased(device, what, stream, FIT_SCRATCH_BYTES, [&](char* base, hipStream_t s) -> int {
         const Pairs in{d_p, d_q, d_pairs, d_opt_count, static_cast<u32>(np), static_cast<u32>(nq), static_cast<u32>(pairs_capacity)};
         const FitSet set{in, d_opt_positions != nullptr, d_opt_positions, d_opt_positions ? d_opt_positions_count : nullptr, static_cast<u32>(positions_capacity)};
-        ScratchLease lease(sh, device, s);
-        int r;
-        if ((r = lease.take(FIT_SCRATCH_BYTES)) != PCPX_OK) return r;
-        if ((r = fit_device(set, static_cast<char*>(lease.p), nullptr, d_out_transform, d_opt_out_rms, s)) != PCPX_OK)
-            return r;
-        return lease.leave_queued();
+        return fit_device(set, base, nullptr, d_out_transform, d_opt_out_rms, s);
     });
 }
 
@@ -702,28 +621,18 @@ int pcpx_rigid_fit(const float* p, uint64_t np, const float* q, uint64_t nq, con
     static const char* what = "pcpx_rigid_fit";
     int st = check_clouds(what, p, np, q, nq, pairs, count);
     if (st != PCPX_OK || (st = check_fit(what, opt_positions, positions_count, out_transform)) != PCPX_OK) return st;
-    if (device < 0 || device >= LEASE_MAX_DEVICES) return select_device(device);
-    return on_shared(device, what, [&](DeviceShared& sh) -> int {
-        PooledStream ps;
-        PCPX_HIP(pooled_stream_get(&ps.s));
-        const hipStream_t s = ps.s;
-        Staged in(sh.pool);
-        DevBuf pos(sh.pool), out(sh.pool);
-        ScratchLease lease(sh, device, s);
+    return on_host_call(device, what, [&](HostCall& call) -> int {
         double host[17];
-        int r;
-        if ((r = in.upload(p, np, q, nq, pairs, count, s)) != PCPX_OK || (r = out.alloc(sizeof(host))) != PCPX_OK ||
-            (positions_count && ((r = pos.alloc(positions_count * sizeof(u32))) != PCPX_OK ||
-                                 (r = upload_pageable(pos.p, opt_positions, positions_count * sizeof(u32), s)) != PCPX_OK)) ||
-            (r = lease.take(FIT_SCRATCH_BYTES)) != PCPX_OK)
-            return r;
+        const Pairs in = staged_pairs(call, p, np, q, nq, pairs, count);
+        double* out = call.alloc<double>(sizeof(host));
+        const u32* pos = call.upload(opt_positions, positions_count * sizeof(u32));
+        char* base = call.scratch(FIT_SCRATCH_BYTES);
         // (a list of no positions is a set of no pairs, not "all correspondences")
-        const FitSet set{in.view(np, nq, count), opt_positions != nullptr, pos.as<u32>(), nullptr, static_cast<u32>(positions_count)};
-        if ((r = fit_device(set, static_cast<char*>(lease.p), nullptr, out.as<double>(), out.as<double>() + 16, s)) !=
-            PCPX_OK)
+        const FitSet set{in, opt_positions != nullptr, pos, nullptr, static_cast<u32>(positions_count)};
+        int r;
+        if ((r = call.st) != PCPX_OK || (r = fit_device(set, base, nullptr, out, out + 16, call.s)) != PCPX_OK ||
+            (r = call.download(host, out, sizeof(host))) != PCPX_OK || (r = call.wait()) != PCPX_OK)
             return r;
-        PCPX_HIP(hipMemcpyAsync(host, out.p, sizeof(host), hipMemcpyDeviceToHost, s));
-        PCPX_HIP(hipStreamSynchronize(s));
         std::copy(host, host + 16, out_transform);
         if (opt_out_rms) *opt_out_rms = host[16];
         return PCPX_OK;

@@ -122,11 +122,11 @@ def test_icp_kernels_use_no_scratch_and_spill_nothing():
     rows = dict((m[0], [int(v) for v in m[1:]]) for m in re.findall(
         r"(k_\w+(?:<[^>]*>)?)\(.*?vgpr\s+(\d+) sgpr\s+(\d+) sspill\s+(\d+) vspill\s+(\d+) scratch\s+(\d+) lds\s+(\d+)", out))
     assert len(out.strip().splitlines()) == len(rows), out  # (every kernel of the file is among them)
-    assert sorted(rows) == ["k_icp_commit", "k_icp_decide", "k_icp_finish", "k_icp_init", "k_icp_moved", "k_nearest_posed", "k_plane_final",
-                            "k_plane_partial", "k_plane_solve"], out
+    assert sorted(rows) == ["k_fixed_final<PlaneSystem>", "k_fixed_partial<PlaneSystem>", "k_icp_commit", "k_icp_decide", "k_icp_finish", "k_icp_init",
+                            "k_icp_moved", "k_nearest_posed", "k_plane_solve"], out
     for name, (vgpr, sgpr, sspill, vspill, scratch, lds) in rows.items():
         assert scratch == 0 and vspill == 0 and sspill == 0, (name, out)
-        assert lds == 0 or name == "k_plane_partial", (name, out)  # (the plane sums' block tree)
+        assert lds == 0 or name == "k_fixed_partial<PlaneSystem>", (name, out)  # (the plane sums' block tree)
         assert vgpr <= 128 and sgpr <= 102, (name, out)
     assert rows["k_nearest_posed"][5] == 0 and rows["k_nearest_posed"][0] <= 64, out  # no LDS, and eight waves a SIMD by its vector registers
 

@@ -204,25 +204,33 @@ def test_planes_kernels_use_no_scratch_and_spill_nothing():
         r"(k_\w+(?:<[^>]*>)?)\(.*?vgpr\s+(\d+) sgpr\s+(\d+) sspill\s+(\d+) vspill\s+(\d+) scratch\s+(\d+) lds\s+(\d+)", out))
     assert len(out.strip().splitlines()) == len(rows), out  # (every kernel of the file is among them)
     own = sorted(set(re.sub(r"<.*", "", name) for name in rows if not name.startswith("k_scan_")))
-    assert own == ["k_pfit_final", "k_pfit_partial", "k_pfit_solve", "k_plane_begin", "k_plane_count", "k_plane_decide", "k_plane_finish", "k_plane_flag", "k_plane_fold",
+    assert own == ["k_fixed_final", "k_fixed_partial", "k_pfit_solve", "k_plane_begin", "k_plane_count", "k_plane_decide", "k_plane_finish", "k_plane_flag", "k_plane_fold",
                    "k_plane_keep", "k_plane_pack", "k_plane_rows", "k_ransac_best", "k_reg_compact"], out
     for name, (vgpr, sgpr, sspill, vspill, scratch, lds) in rows.items():
         assert scratch == 0 and vspill == 0 and sspill == 0, (name, out)
-        assert lds == 0 or name.startswith(("k_scan_", "k_pfit_partial")), (name, out)  # (the scan's and the fit's block sums)
+        assert lds == 0 or name.startswith(("k_scan_", "k_fixed_partial")), (name, out)  # (the scan's and the fit's block sums)
         assert vgpr <= 128 and sgpr <= 102, (name, out)
     for name in ("k_plane_count<true>", "k_plane_count<false>"):
         assert rows[name][5] == 0 and rows[name][0] <= 64, out  # no LDS, and eight waves a SIMD by its vector registers
 
 
 def test_register_still_shares_the_moved_kernels():
-    """k_ransac_best and k_reg_compact live in one header that both files include; neither file has a copy"""
+    """k_ransac_best and k_reg_compact live in one header that both files include; neither file has a copy.  Nor has any file a copy
+    of the fixed order of the fits' float64 sums: the block tree, the block-order loop and the clamped count are pcpx_fixed_sum.h's."""
     csrc = os.path.join(ROOT, "point-cloud-processing_amd", "csrc")
     for name in ("pcpx_register.hip", "pcpx_planes.hip"):
         text = open(os.path.join(csrc, name)).read()
         assert '#include "pcpx_ransac.h"' in text and "void k_ransac_best" not in text and "void k_reg_compact" not in text, name
         assert "k_ransac_best<<<" in text and "k_reg_compact<<<" in text, name
     shared = open(os.path.join(csrc, "pcpx_ransac.h")).read()
-    assert shared.count("void k_ransac_best") == 1 and shared.count("void k_reg_compact") == 1 and "fit_block_sums" in shared
+    assert shared.count("void k_ransac_best") == 1 and shared.count("void k_reg_compact") == 1 and '#include "pcpx_fixed_sum.h"' in shared
+    once = ("__shared__ double tree", "tree[threadIdx.x] += tree[threadIdx.x + off]", "b < FIT_BLOCKS; ++b", "u32 clamped_count(")
+    fixed = open(os.path.join(csrc, "pcpx_fixed_sum.h")).read()
+    assert all(fixed.count(text) == 1 for text in once), [fixed.count(text) for text in once]
+    for name in sorted(os.listdir(csrc)):
+        if name != "pcpx_fixed_sum.h":
+            text = open(os.path.join(csrc, name)).read()
+            assert not any(t in text for t in once), name
 
 
 def test_cpp_planes_program_compiles(tmp_path, pkg):

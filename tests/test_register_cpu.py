@@ -167,10 +167,10 @@ def test_register_kernels_use_no_scratch_and_spill_nothing():
         r"(k_\w+(?:<[^>]*>)?)\(.*?vgpr\s+(\d+) sgpr\s+(\d+) sspill\s+(\d+) vspill\s+(\d+) scratch\s+(\d+) lds\s+(\d+)", out))
     assert len(out.strip().splitlines()) == len(rows), out  # (every kernel of the file is among them)
     own = sorted(set(re.sub(r"<.*", "", name) for name in rows if not name.startswith("k_scan_")))
-    assert own == ["k_fit_final", "k_fit_partial", "k_fit_solve", "k_ransac_best", "k_ransac_count", "k_ransac_emit", "k_reg_compact", "k_reg_pack"], out
+    assert own == ["k_fit_solve", "k_fixed_final", "k_fixed_partial", "k_ransac_best", "k_ransac_count", "k_ransac_emit", "k_reg_compact", "k_reg_pack"], out
     for name, (vgpr, sgpr, sspill, vspill, scratch, lds) in rows.items():
         assert scratch == 0 and vspill == 0 and sspill == 0, (name, out)
-        assert lds == 0 or name.startswith(("k_scan_", "k_fit_partial")), (name, out)  # (the scan's and the fit's block sums)
+        assert lds == 0 or name.startswith(("k_scan_", "k_fixed_partial")), (name, out)  # (the scan's and the fit's block sums)
         assert vgpr <= 128 and sgpr <= 102, (name, out)
     assert rows["k_ransac_count"][5] == 0 and rows["k_ransac_count"][0] <= 64, out  # no LDS, and eight waves a SIMD by its vector registers
 

@@ -38,7 +38,7 @@ TAU, SEED = 0.01, 0x1234
 # vector instructions of one record in k_plane_count's loop, counted in the disassembly, and the estimate from them
 VALU_PER_RECORD, CLOCK_GHZ, SIMDS = 8, 2.4, 1024
 ESTIMATE = SIMDS * CLOCK_GHZ * 1e9 / (VALU_PER_RECORD * 2) * 64
-KERNELS = r"\b(k_plane_[a-z_]+|k_ransac_[a-z_]+|k_reg_[a-z_]+|k_pfit_[a-z_]+|k_scan_[a-z_]+)"
+KERNELS = r"\b(k_plane_[a-z_]+|k_ransac_[a-z_]+|k_reg_[a-z_]+|k_pfit_[a-z_]+|k_fixed_[a-z_]+|k_scan_[a-z_]+)"
 
 
 def summarise():

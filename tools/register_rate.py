@@ -31,7 +31,7 @@ a = ap.parse_args()
 CASES = ((100_000, 1_000), (1_000_000, 10_000), (4_000_000, 1_000))  # (hypotheses, correspondences)
 TRACE_CALLS = 3
 TAU, SIMILARITY, SEED = 0.01, 0.9, 0x1234
-KERNELS = r"\b(k_reg_[a-z_]+|k_ransac_[a-z_]+|k_fit_[a-z_]+(?:<\d>)?|k_scan_[a-z_]+)"
+KERNELS = r"\b(k_reg_[a-z_]+|k_ransac_[a-z_]+|k_fit_[a-z_]+|k_fixed_[a-z_]+(?:<\w+>)?|k_scan_[a-z_]+)"
 
 
 def summarise():
