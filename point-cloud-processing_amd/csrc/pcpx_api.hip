@@ -1,13 +1,12 @@
 // pcpx_api.hip -- the extern "C" boundary declared in include/pcpx.h (and its companions include/pcpx_radius.h and include/pcpx_features.h).
 // Host-pointer entry points stage through device buffers and are synchronous; *_dev entry points
 // enqueue on the index's stream.  No CPU fallback exists: every compute call needs a HIP device.
-#include "pcpx_internal.h"
+#include "pcpx_stage.h"
 #include "pcpx_radius.h"
 #include "pcpx_features.h"
 
 #include <algorithm>
 #include <cstring>
-#include <functional>
 #include <vector>
 
 namespace pcpx {
@@ -1220,11 +1219,27 @@ int pcpx_device_download(void* dst, const void* d_src, uint64_t bytes, int devic
 }
 
 // ---- fixed-radius neighbourhoods (include/pcpx_radius.h): the moments form of the sphere walk ------------------------------------
-static int check_radius(const char* what, float radius)
+static int no_outputs(const char* what)
 {
-    if (radius >= 0.f) return PCPX_OK;  // (false for NaN)
-    set_error("%s: the radius must be >= 0 (got %g)", what, static_cast<double>(radius));
+    set_error("%s: every output is NULL", what);
     return PCPX_ERR_INVALID;
+}
+
+// The moments form for the curve positions of slice `sl`, by input row, on the handle's stream: what both forms below run
+static int range_neighbourhoods_self(Index& ix, float radius, const Slice& sl, float* d_opt_normals, float* d_opt_centroids,
+                                     float* d_opt_mean_dist, u32* d_opt_count)
+{
+    int st;
+    if (sl.lo == 0 && sl.hi == ix.n && ix.n != ix.n_in) {  // the whole curve order: the rows of the points outside the grid too
+        if ((st = ensure_gather_arrays(ix, sizeof(u32))) != PCPX_OK) return st;
+        if ((st = launch_range_moments_empty_rows(ix, ix.d_pos_of, ix.n_in, d_opt_normals, d_opt_centroids, d_opt_mean_dist, d_opt_count)) !=
+            PCPX_OK)
+            return st;
+    }
+    QueryView qv = self_view(ix);
+    qv.pos_lo = static_cast<u32>(sl.lo);
+    qv.pos_hi = static_cast<u32>(sl.hi);
+    return launch_range_moments(ix, qv, true, sl.gf, sl.gc, radius, nullptr, d_opt_normals, d_opt_centroids, d_opt_mean_dist, d_opt_count);
 }
 
 int pcpx_range_neighbourhoods_self_dev(pcpx_index* h, float radius, uint64_t sorted_first, uint64_t sorted_count,
@@ -1233,72 +1248,47 @@ int pcpx_range_neighbourhoods_self_dev(pcpx_index* h, float radius, uint64_t sor
     static const char* what = "pcpx_range_neighbourhoods_self_dev";
     return on_index(h, what, WHOLE_CLOUD, [&](Index* ix) -> int {
     int st;
-    if (!d_opt_normals && !d_opt_centroids && !d_opt_mean_dist && !d_opt_count) {
-        set_error("%s: every output is NULL", what);
-        return PCPX_ERR_INVALID;
-    }
+    if (!d_opt_normals && !d_opt_centroids && !d_opt_mean_dist && !d_opt_count) return no_outputs(what);
     if ((st = check_radius(what, radius)) != PCPX_OK) return st;
     if ((st = check_slice(what, sorted_first)) != PCPX_OK) return st;
-    const Slice sl = slice_of(*ix, sorted_first, sorted_count);
-    if (sl.lo == 0 && sl.hi == ix->n && ix->n != ix->n_in) {  // the whole curve order: the rows of the points outside the grid too
-        if ((st = ensure_gather_arrays(*ix, sizeof(u32))) != PCPX_OK) return st;
-        if ((st = launch_range_moments_empty_rows(*ix, ix->d_pos_of, ix->n_in, d_opt_normals, d_opt_centroids, d_opt_mean_dist,
-                                                  d_opt_count)) != PCPX_OK)
-            return st;
-    }
-    QueryView qv = self_view(*ix);
-    qv.pos_lo = static_cast<u32>(sl.lo);
-    qv.pos_hi = static_cast<u32>(sl.hi);
-    return launch_range_moments(*ix, qv, true, sl.gf, sl.gc, radius, nullptr, d_opt_normals, d_opt_centroids, d_opt_mean_dist,
-                                d_opt_count);
+    return range_neighbourhoods_self(*ix, radius, slice_of(*ix, sorted_first, sorted_count), d_opt_normals, d_opt_centroids, d_opt_mean_dist,
+                                     d_opt_count);
     });
 }
 
-// Host outputs: one device block per asked output, then the copies back
-struct MomentsHost {
-    float* normals;
-    float* centroids;
-    float* mean_dist;
-    uint32_t* count;
-};
-static int moments_to_host(Index* ix, u64 rows, const MomentsHost& out, const std::function<int(float*, float*, float*, u32*)>& run)
+// Host outputs of the moments form: one device block per asked output, `run` fills them, then the copies back and the wait
+extern "C++" template <class Run>
+static int moments_staged(Staged& stage, u64 rows, float* normals, float* centroids, float* mean_dist, u32* count, Run&& run)
 {
     int st;
-    DevBuf dn(ix->pool), dc(ix->pool), dm(ix->pool), dk(ix->pool);
-    if (out.normals && (st = dn.alloc(rows * 3 * sizeof(float))) != PCPX_OK) return st;
-    if (out.centroids && (st = dc.alloc(rows * 3 * sizeof(float))) != PCPX_OK) return st;
-    if (out.mean_dist && (st = dm.alloc(rows * sizeof(float))) != PCPX_OK) return st;
-    if (out.count && (st = dk.alloc(rows * sizeof(u32))) != PCPX_OK) return st;
-    if ((st = run(dn.as<float>(), dc.as<float>(), dm.as<float>(), dk.as<u32>())) != PCPX_OK) return st;
-    if (out.normals) PCPX_HIP(hipMemcpyAsync(out.normals, dn.p, rows * 3 * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
-    if (out.centroids) PCPX_HIP(hipMemcpyAsync(out.centroids, dc.p, rows * 3 * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
-    if (out.mean_dist) PCPX_HIP(hipMemcpyAsync(out.mean_dist, dm.p, rows * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
-    if (out.count) PCPX_HIP(hipMemcpyAsync(out.count, dk.p, rows * sizeof(u32), hipMemcpyDeviceToHost, ix->stream));
-    PCPX_HIP(hipStreamSynchronize(ix->stream));
-    return PCPX_OK;
+    float* dn = stage.alloc_for(normals, rows * 3 * sizeof(float));
+    float* dc = stage.alloc_for(centroids, rows * 3 * sizeof(float));
+    float* dm = stage.alloc_for(mean_dist, rows * sizeof(float));
+    u32* dk = stage.alloc_for(count, rows * sizeof(u32));
+    if ((st = stage.st) != PCPX_OK || (st = run(dn, dc, dm, dk)) != PCPX_OK) return st;
+    stage.download_opt(normals, dn, rows * 3 * sizeof(float));
+    stage.download_opt(centroids, dc, rows * 3 * sizeof(float));
+    stage.download_opt(mean_dist, dm, rows * sizeof(float));
+    stage.download_opt(count, dk, rows * sizeof(u32));
+    return stage.wait();
 }
 
 int pcpx_range_neighbourhoods_self(pcpx_index* h, float radius, float* opt_normals, float* opt_centroids, float* opt_mean_dist,
                                    uint32_t* opt_count)
 {
     static const char* what = "pcpx_range_neighbourhoods_self";
-    return on_index(h, what, WHOLE_CLOUD, [&](Index* ix) -> int {
+    return on_index_host(h, what, WHOLE_CLOUD, [&](Index* ix, Staged& stage) -> int {
     int st;
-    if (!opt_normals && !opt_centroids && !opt_mean_dist && !opt_count) {
-        set_error("%s: every output is NULL", what);
-        return PCPX_ERR_INVALID;
-    }
+    if (!opt_normals && !opt_centroids && !opt_mean_dist && !opt_count) return no_outputs(what);
     if ((st = check_radius(what, radius)) != PCPX_OK) return st;
     if (ix->n_in == 0) return PCPX_OK;
-    return moments_to_host(ix, ix->n_in, MomentsHost{opt_normals, opt_centroids, opt_mean_dist, opt_count},
-                           [&](float* dn, float* dc, float* dm, u32* dk) {
-                               return pcpx_range_neighbourhoods_self_dev(h, radius, 0, UINT64_MAX, dn, dc, dm, dk);
-                           });
+    return moments_staged(stage, ix->n_in, opt_normals, opt_centroids, opt_mean_dist, opt_count, [&](float* dn, float* dc, float* dm, u32* dk) {
+        return range_neighbourhoods_self(*ix, radius, slice_of(*ix, 0, UINT64_MAX), dn, dc, dm, dk);
+    });
     });
 }
 
-// The batch forms' spheres: checked (every radius >= 0), then on the device (dq, dr: the caller's, alive until its launch is
-// enqueued) and prepared as queries; nq > 0
+// The batch forms' spheres: checked (every radius >= 0) ...
 static int check_spheres(const char* what, const float* q_xyz, const float* radii, float radius, u64 nq)
 {
     if (nq > 0 && !q_xyz) return PCPX_ERR_INVALID;
@@ -1313,38 +1303,29 @@ static int check_spheres(const char* what, const float* q_xyz, const float* radi
     }
     return PCPX_OK;
 }
-static int upload_spheres(Index* ix, const float* q_xyz, const float* radii, u64 nq, DevBuf& dq, DevBuf& dr, QueryView& qv)
+// ... then staged on the device (*d_radii: null without a radii array) and prepared as queries; nq > 0
+static int stage_spheres(Index& ix, Staged& stage, const float* q_xyz, const float* radii, u64 nq, const float** d_radii, QueryView& qv)
 {
-    int st;
-    if ((st = dq.alloc(nq * 3 * sizeof(float))) != PCPX_OK) return st;
-    if ((st = upload_pageable(dq.p, q_xyz, nq * 3 * sizeof(float), ix->stream)) != PCPX_OK) return st;
-    if (radii) {
-        if ((st = dr.alloc(nq * sizeof(float))) != PCPX_OK) return st;
-        if ((st = upload_pageable(dr.p, radii, nq * sizeof(float), ix->stream)) != PCPX_OK) return st;
-    }
-    return prepare_queries(*ix, dq.as<float>(), nq, qv);
+    const float* dq = stage.upload(q_xyz, nq * 3 * sizeof(float));
+    *d_radii = stage.upload(radii, nq * sizeof(float));
+    return stage.st != PCPX_OK ? stage.st : prepare_queries(ix, dq, nq, qv);
 }
 
 int pcpx_range_neighbourhoods_batch(pcpx_index* h, const float* q_xyz, const float* radii, float radius, uint64_t nq,
                                     float* opt_normals, float* opt_centroids, float* opt_mean_dist, uint32_t* opt_count)
 {
     static const char* what = "pcpx_range_neighbourhoods_batch";
-    return on_index(h, what, WHOLE_CLOUD, [&](Index* ix) -> int {
+    return on_index_host(h, what, WHOLE_CLOUD, [&](Index* ix, Staged& stage) -> int {
     int st;
-    if (!opt_normals && !opt_centroids && !opt_mean_dist && !opt_count) {
-        set_error("%s: every output is NULL", what);
-        return PCPX_ERR_INVALID;
-    }
+    if (!opt_normals && !opt_centroids && !opt_mean_dist && !opt_count) return no_outputs(what);
     if ((st = check_spheres(what, q_xyz, radii, radius, nq)) != PCPX_OK) return st;
     if (nq == 0) return PCPX_OK;
-    DevBuf dq(ix->pool), dr(ix->pool);
+    const float* dr;
     QueryView qv;
-    if ((st = upload_spheres(ix, q_xyz, radii, nq, dq, dr, qv)) != PCPX_OK) return st;
-    return moments_to_host(ix, nq, MomentsHost{opt_normals, opt_centroids, opt_mean_dist, opt_count},
-                           [&](float* dn, float* dc, float* dm, u32* dk) {
-                               return launch_range_moments(*ix, qv, false, 0, (nq + GROUP - 1) / GROUP, radius, dr.as<float>(), dn, dc,
-                                                           dm, dk);
-                           });
+    if ((st = stage_spheres(*ix, stage, q_xyz, radii, nq, &dr, qv)) != PCPX_OK) return st;
+    return moments_staged(stage, nq, opt_normals, opt_centroids, opt_mean_dist, opt_count, [&](float* dn, float* dc, float* dm, u32* dk) {
+        return launch_range_moments(*ix, qv, false, 0, (nq + GROUP - 1) / GROUP, radius, dr, dn, dc, dm, dk);
+    });
     });
 }
 
@@ -1357,11 +1338,21 @@ struct FeaturesPtrs {
     uint32_t* count;
     bool none() const { return !evals && !curvature && !normals && !axes && !count; }
 };
-static int check_features_outputs(const char* what, const FeaturesPtrs& out)
+static int check_features_outputs(const char* what, const FeaturesPtrs& out) { return out.none() ? no_outputs(what) : PCPX_OK; }
+
+// The features form for the curve positions of slice `sl`, by input row, on the handle's stream: what both forms below run
+static int shape_features_self(Index& ix, float radius, const Slice& sl, const FeaturesPtrs& d)
 {
-    if (!out.none()) return PCPX_OK;
-    set_error("%s: every output is NULL", what);
-    return PCPX_ERR_INVALID;
+    int st;
+    if (sl.lo == 0 && sl.hi == ix.n && ix.n != ix.n_in) {  // the whole curve order: the rows of the points outside the grid too
+        if ((st = ensure_gather_arrays(ix, sizeof(u32))) != PCPX_OK) return st;
+        if ((st = launch_range_features_empty_rows(ix, ix.d_pos_of, ix.n_in, d.evals, d.curvature, d.normals, d.axes, d.count)) != PCPX_OK)
+            return st;
+    }
+    QueryView qv = self_view(ix);
+    qv.pos_lo = static_cast<u32>(sl.lo);
+    qv.pos_hi = static_cast<u32>(sl.hi);
+    return launch_range_features(ix, qv, true, sl.gf, sl.gc, radius, nullptr, d.evals, d.curvature, d.normals, d.axes, d.count);
 }
 
 int pcpx_shape_features_self_dev(pcpx_index* h, float radius, uint64_t sorted_first, uint64_t sorted_count, float* d_opt_evals,
@@ -1370,57 +1361,43 @@ int pcpx_shape_features_self_dev(pcpx_index* h, float radius, uint64_t sorted_fi
     static const char* what = "pcpx_shape_features_self_dev";
     return on_index(h, what, WHOLE_CLOUD, [&](Index* ix) -> int {
     int st;
-    if ((st = check_features_outputs(what, FeaturesPtrs{d_opt_evals, d_opt_curvature, d_opt_normals, d_opt_axes, d_opt_count})) != PCPX_OK)
-        return st;
+    const FeaturesPtrs d{d_opt_evals, d_opt_curvature, d_opt_normals, d_opt_axes, d_opt_count};
+    if ((st = check_features_outputs(what, d)) != PCPX_OK) return st;
     if ((st = check_radius(what, radius)) != PCPX_OK) return st;
     if ((st = check_slice(what, sorted_first)) != PCPX_OK) return st;
-    const Slice sl = slice_of(*ix, sorted_first, sorted_count);
-    if (sl.lo == 0 && sl.hi == ix->n && ix->n != ix->n_in) {  // the whole curve order: the rows of the points outside the grid too
-        if ((st = ensure_gather_arrays(*ix, sizeof(u32))) != PCPX_OK) return st;
-        if ((st = launch_range_features_empty_rows(*ix, ix->d_pos_of, ix->n_in, d_opt_evals, d_opt_curvature, d_opt_normals, d_opt_axes,
-                                                   d_opt_count)) != PCPX_OK)
-            return st;
-    }
-    QueryView qv = self_view(*ix);
-    qv.pos_lo = static_cast<u32>(sl.lo);
-    qv.pos_hi = static_cast<u32>(sl.hi);
-    return launch_range_features(*ix, qv, true, sl.gf, sl.gc, radius, nullptr, d_opt_evals, d_opt_curvature, d_opt_normals, d_opt_axes,
-                                 d_opt_count);
+    return shape_features_self(*ix, radius, slice_of(*ix, sorted_first, sorted_count), d);
     });
 }
 
-// Host outputs: one device block per asked output, then the copies back
-static int features_to_host(Index* ix, u64 rows, const FeaturesPtrs& out, const std::function<int(const FeaturesPtrs&)>& run)
+// Host outputs of the features form: one device block per asked output, `run` fills them, then the copies back and the wait
+extern "C++" template <class Run>
+static int features_staged(Staged& stage, u64 rows, const FeaturesPtrs& out, Run&& run)
 {
     int st;
-    DevBuf de(ix->pool), dv(ix->pool), dn(ix->pool), da(ix->pool), dk(ix->pool);
-    if (out.evals && (st = de.alloc(rows * 3 * sizeof(float))) != PCPX_OK) return st;
-    if (out.curvature && (st = dv.alloc(rows * sizeof(float))) != PCPX_OK) return st;
-    if (out.normals && (st = dn.alloc(rows * 3 * sizeof(float))) != PCPX_OK) return st;
-    if (out.axes && (st = da.alloc(rows * 3 * sizeof(float))) != PCPX_OK) return st;
-    if (out.count && (st = dk.alloc(rows * sizeof(u32))) != PCPX_OK) return st;
-    if ((st = run(FeaturesPtrs{de.as<float>(), dv.as<float>(), dn.as<float>(), da.as<float>(), dk.as<u32>()})) != PCPX_OK) return st;
-    if (out.evals) PCPX_HIP(hipMemcpyAsync(out.evals, de.p, rows * 3 * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
-    if (out.curvature) PCPX_HIP(hipMemcpyAsync(out.curvature, dv.p, rows * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
-    if (out.normals) PCPX_HIP(hipMemcpyAsync(out.normals, dn.p, rows * 3 * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
-    if (out.axes) PCPX_HIP(hipMemcpyAsync(out.axes, da.p, rows * 3 * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
-    if (out.count) PCPX_HIP(hipMemcpyAsync(out.count, dk.p, rows * sizeof(u32), hipMemcpyDeviceToHost, ix->stream));
-    PCPX_HIP(hipStreamSynchronize(ix->stream));
-    return PCPX_OK;
+    const FeaturesPtrs d{stage.alloc_for(out.evals, rows * 3 * sizeof(float)), stage.alloc_for(out.curvature, rows * sizeof(float)),
+                         stage.alloc_for(out.normals, rows * 3 * sizeof(float)), stage.alloc_for(out.axes, rows * 3 * sizeof(float)),
+                         stage.alloc_for(out.count, rows * sizeof(u32))};
+    if ((st = stage.st) != PCPX_OK || (st = run(d)) != PCPX_OK) return st;
+    stage.download_opt(out.evals, d.evals, rows * 3 * sizeof(float));
+    stage.download_opt(out.curvature, d.curvature, rows * sizeof(float));
+    stage.download_opt(out.normals, d.normals, rows * 3 * sizeof(float));
+    stage.download_opt(out.axes, d.axes, rows * 3 * sizeof(float));
+    stage.download_opt(out.count, d.count, rows * sizeof(u32));
+    return stage.wait();
 }
 
 int pcpx_shape_features_self(pcpx_index* h, float radius, float* opt_evals, float* opt_curvature, float* opt_normals, float* opt_axes,
                              uint32_t* opt_count)
 {
     static const char* what = "pcpx_shape_features_self";
-    return on_index(h, what, WHOLE_CLOUD, [&](Index* ix) -> int {
+    return on_index_host(h, what, WHOLE_CLOUD, [&](Index* ix, Staged& stage) -> int {
     int st;
     const FeaturesPtrs out{opt_evals, opt_curvature, opt_normals, opt_axes, opt_count};
     if ((st = check_features_outputs(what, out)) != PCPX_OK) return st;
     if ((st = check_radius(what, radius)) != PCPX_OK) return st;
     if (ix->n_in == 0) return PCPX_OK;
-    return features_to_host(ix, ix->n_in, out, [&](const FeaturesPtrs& d) {
-        return pcpx_shape_features_self_dev(h, radius, 0, UINT64_MAX, d.evals, d.curvature, d.normals, d.axes, d.count);
+    return features_staged(stage, ix->n_in, out, [&](const FeaturesPtrs& d) {
+        return shape_features_self(*ix, radius, slice_of(*ix, 0, UINT64_MAX), d);
     });
     });
 }
@@ -1429,18 +1406,17 @@ int pcpx_shape_features_batch(pcpx_index* h, const float* q_xyz, const float* ra
                               float* opt_curvature, float* opt_normals, float* opt_axes, uint32_t* opt_count)
 {
     static const char* what = "pcpx_shape_features_batch";
-    return on_index(h, what, WHOLE_CLOUD, [&](Index* ix) -> int {
+    return on_index_host(h, what, WHOLE_CLOUD, [&](Index* ix, Staged& stage) -> int {
     int st;
     const FeaturesPtrs out{opt_evals, opt_curvature, opt_normals, opt_axes, opt_count};
     if ((st = check_features_outputs(what, out)) != PCPX_OK) return st;
     if ((st = check_spheres(what, q_xyz, radii, radius, nq)) != PCPX_OK) return st;
     if (nq == 0) return PCPX_OK;
-    DevBuf dq(ix->pool), dr(ix->pool);
+    const float* dr;
     QueryView qv;
-    if ((st = upload_spheres(ix, q_xyz, radii, nq, dq, dr, qv)) != PCPX_OK) return st;
-    return features_to_host(ix, nq, out, [&](const FeaturesPtrs& d) {
-        return launch_range_features(*ix, qv, false, 0, (nq + GROUP - 1) / GROUP, radius, dr.as<float>(), d.evals, d.curvature, d.normals,
-                                     d.axes, d.count);
+    if ((st = stage_spheres(*ix, stage, q_xyz, radii, nq, &dr, qv)) != PCPX_OK) return st;
+    return features_staged(stage, nq, out, [&](const FeaturesPtrs& d) {
+        return launch_range_features(*ix, qv, false, 0, (nq + GROUP - 1) / GROUP, radius, dr, d.evals, d.curvature, d.normals, d.axes, d.count);
     });
     });
 }

@@ -106,10 +106,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void k_cluster_border(TreeVie
 
 int check_cluster_args(const char* what, float radius, u32 min_pts, u32 flags, const void* labels)
 {
-    if (!(radius >= 0.f)) {  // (false for NaN)
-        set_error("%s: the radius must be >= 0 (got %g)", what, static_cast<double>(radius));
-        return PCPX_ERR_INVALID;
-    }
+    if (const int st = check_radius(what, radius)) return st;
     if (min_pts == 0) {
         set_error("%s: min_pts must be >= 1", what);
         return PCPX_ERR_INVALID;
@@ -141,12 +138,14 @@ int cluster_self(Index& ix, float radius, u32 min_pts, u32 flags, u32* d_labels,
     }
     const u64 npos = static_cast<u64>(ix.nleaves) * LEAF;  // >= n
     const u32 ntiles = scan_tiles(rows);
-    auto padded = [](u64 words) { return (words * sizeof(u32) + 255) / 256 * 256; };
-    const size_t parent_bytes = padded(npos > rows ? npos : rows), aux_bytes = padded(npos ? npos : 1), sums_bytes = padded(ntiles + 1);
-    if ((st = ensure_scratch(ix, parent_bytes + aux_bytes + sums_bytes)) != PCPX_OK) return st;
-    u32* parent = static_cast<u32*>(ix.d_scratch);
-    u32* aux = reinterpret_cast<u32*>(static_cast<char*>(ix.d_scratch) + parent_bytes);
-    u32* sums = reinterpret_cast<u32*>(static_cast<char*>(ix.d_scratch) + parent_bytes + aux_bytes);
+    Carve c;
+    const size_t parent_at = c.take((npos > rows ? npos : rows) * sizeof(u32)), aux_at = c.take((npos ? npos : 1) * sizeof(u32)),
+                 sums_at = c.take((ntiles + 1ull) * sizeof(u32));
+    if ((st = ensure_scratch(ix, c.bytes())) != PCPX_OK) return st;
+    char* base = static_cast<char*>(ix.d_scratch);
+    u32* parent = reinterpret_cast<u32*>(base + parent_at);
+    u32* aux = reinterpret_cast<u32*>(base + aux_at);
+    u32* sums = reinterpret_cast<u32*>(base + sums_at);
     if (n != rows) {  // the rows of the points outside the voxel grid: noise, not core, count 0
         PCPX_HIP(hipMemsetAsync(d_labels, 0xFF, rows * sizeof(u32), s));
         if (d_core) PCPX_HIP(hipMemsetAsync(d_core, 0, rows * sizeof(uint8_t), s));
@@ -203,24 +202,22 @@ int pcpx_cluster_self(pcpx_index* h, float radius, uint32_t min_pts, uint32_t fl
                       uint32_t* opt_count, uint64_t* opt_cluster_count)
 {
     static const char* what = "pcpx_cluster_self";
-    return on_index(h, what, WHOLE_CLOUD, [&](Index* ix) -> int {
+    return on_index_host(h, what, WHOLE_CLOUD, [&](Index* ix, Staged& stage) -> int {
         int st;
         if ((st = check_cluster_args(what, radius, min_pts, flags, labels)) != PCPX_OK) return st;
         if (opt_cluster_count) *opt_cluster_count = 0;
         const u64 rows = ix->n_in;
         if (rows == 0) return PCPX_OK;
-        DevBuf dl(ix->pool), dc(ix->pool), dk(ix->pool), dt(ix->pool);
-        if ((st = dl.alloc(rows * sizeof(u32))) != PCPX_OK) return st;
-        if (opt_core && (st = dc.alloc(rows * sizeof(uint8_t))) != PCPX_OK) return st;
-        if (opt_count && (st = dk.alloc(rows * sizeof(u32))) != PCPX_OK) return st;
-        if (opt_cluster_count && (st = dt.alloc(sizeof(u64))) != PCPX_OK) return st;
-        if ((st = cluster_self(*ix, radius, min_pts, flags, dl.as<u32>(), dc.as<uint8_t>(), dk.as<u32>(), dt.as<u64>())) != PCPX_OK) return st;
-        PCPX_HIP(hipMemcpyAsync(labels, dl.p, rows * sizeof(u32), hipMemcpyDeviceToHost, ix->stream));
-        if (opt_core) PCPX_HIP(hipMemcpyAsync(opt_core, dc.p, rows * sizeof(uint8_t), hipMemcpyDeviceToHost, ix->stream));
-        if (opt_count) PCPX_HIP(hipMemcpyAsync(opt_count, dk.p, rows * sizeof(u32), hipMemcpyDeviceToHost, ix->stream));
-        if (opt_cluster_count) PCPX_HIP(hipMemcpyAsync(opt_cluster_count, dt.p, sizeof(u64), hipMemcpyDeviceToHost, ix->stream));
-        PCPX_HIP(hipStreamSynchronize(ix->stream));
-        return PCPX_OK;
+        u32* dl = stage.alloc<u32>(rows * sizeof(u32));
+        uint8_t* dc = stage.alloc_for(opt_core, rows * sizeof(uint8_t));
+        u32* dk = stage.alloc_for(opt_count, rows * sizeof(u32));
+        u64* dt = stage.alloc_for(opt_cluster_count, sizeof(u64));
+        if ((st = stage.st) != PCPX_OK || (st = cluster_self(*ix, radius, min_pts, flags, dl, dc, dk, dt)) != PCPX_OK) return st;
+        stage.download(labels, dl, rows * sizeof(u32));
+        stage.download_opt(opt_core, dc, rows * sizeof(uint8_t));
+        stage.download_opt(opt_count, dk, rows * sizeof(u32));
+        stage.download_opt(opt_cluster_count, dt, sizeof(u64));
+        return stage.wait();
     });
 }
 

@@ -7,6 +7,7 @@
 // A subset of rows is described by the same two kernels with the other lanes idle: k_fpfh_mark first walks the described points'
 // spheres and marks the positions whose SPFH the second walk will read.
 #include "pcpx_device.h"
+#include "pcpx_stage.h"
 #include "pcpx_descriptors.h"
 
 namespace pcpx {
@@ -17,15 +18,6 @@ constexpr u32 FP_BLOCK = 256;
 constexpr int NB = PCPX_FPFH_BINS;   // bins per feature
 constexpr int NF = PCPX_FPFH_SIZE;   // floats per descriptor
 static_assert(NF == 3 * NB, "three features");
-
-// The normals of a leaf's eight points by curve position, SoA like the leaf record itself: one 96-byte scalar load per leaf (this
-// file's own copy of pcpx_segment.hip's record).
-struct Normals8 {
-    float x[LEAF];
-    float y[LEAF];
-    float z[LEAF];
-};
-static_assert(sizeof(Normals8) == 12 * LEAF, "normal record must be dense");
 
 // The SPFH of one curve position: what k_spfh leaves for k_fpfh, 132 bytes per leaf slot.
 struct Spfh {
@@ -245,15 +237,9 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void k_fpfh(TreeView t, u32 g
     }
 }
 
-inline u32 blocks_of(u64 n, u32 per) { return static_cast<u32>((n + per - 1) / per); }
-inline size_t padded(u64 bytes) { return (bytes + 255) / 256 * 256; }
-
 int check_fpfh_args(const char* what, const void* normals, float radius, const void* rows, u64 m, u32 flags, const void* fpfh)
 {
-    if (!(radius >= 0.f)) {  // (false for NaN)
-        set_error("%s: the radius must be >= 0 (got %g)", what, static_cast<double>(radius));
-        return PCPX_ERR_INVALID;
-    }
+    if (const int st = check_radius(what, radius)) return st;
     if (flags != 0u) {
         set_error("%s: unknown flag bits 0x%x", what, flags);
         return PCPX_ERR_INVALID;
@@ -294,16 +280,17 @@ int fpfh_self(Index& ix, const float* d_normals, float radius, bool subset, cons
     }
     if (n == 0 || out_rows == 0) return PCPX_OK;
     const u64 npos = static_cast<u64>(ix.nleaves) * LEAF;  // >= n
-    const size_t spfh_bytes = padded(npos * sizeof(Spfh)), nrec_bytes = padded(ix.nleaves * sizeof(Normals8));
-    const size_t described_bytes = subset ? padded(npos * sizeof(u32)) : 0, needed_bytes = subset ? padded(npos) : 0,
-                 pos_of_bytes = subset ? padded(rows * sizeof(u32)) : 0;
-    if ((st = ensure_scratch(ix, spfh_bytes + nrec_bytes + described_bytes + needed_bytes + pos_of_bytes)) != PCPX_OK) return st;
+    Carve c;
+    const size_t spfh_off = c.take(npos * sizeof(Spfh)), nrec_off = c.take(ix.nleaves * sizeof(Normals8));
+    const size_t described_off = subset ? c.take(npos * sizeof(u32)) : 0, needed_off = subset ? c.take(npos) : 0,
+                 pos_of_off = subset ? c.take(rows * sizeof(u32)) : 0;
+    if ((st = ensure_scratch(ix, c.bytes())) != PCPX_OK) return st;
     char* base = static_cast<char*>(ix.d_scratch);
-    Spfh* spfh_at = reinterpret_cast<Spfh*>(base);
-    Normals8* nrec = reinterpret_cast<Normals8*>(base + spfh_bytes);
-    u32* described = subset ? reinterpret_cast<u32*>(base + spfh_bytes + nrec_bytes) : nullptr;
-    uint8_t* needed = subset ? reinterpret_cast<uint8_t*>(base + spfh_bytes + nrec_bytes + described_bytes) : nullptr;
-    u32* position_of = subset ? reinterpret_cast<u32*>(base + spfh_bytes + nrec_bytes + described_bytes + needed_bytes) : nullptr;
+    Spfh* spfh_at = reinterpret_cast<Spfh*>(base + spfh_off);
+    Normals8* nrec = reinterpret_cast<Normals8*>(base + nrec_off);
+    u32* described = subset ? reinterpret_cast<u32*>(base + described_off) : nullptr;
+    uint8_t* needed = subset ? reinterpret_cast<uint8_t*>(base + needed_off) : nullptr;
+    u32* position_of = subset ? reinterpret_cast<u32*>(base + pos_of_off) : nullptr;
     const TreeView t = ix.view();
     const u32 groups = static_cast<u32>((n + GROUP - 1) / GROUP);
     const u32 grid = grid_for_groups(groups);
@@ -344,7 +331,7 @@ int pcpx_fpfh_self(pcpx_index* h, const float* normals, float radius, const uint
                    float* opt_spfh, uint32_t* opt_pairs)
 {
     static const char* what = "pcpx_fpfh_self";
-    return on_index(h, what, WHOLE_CLOUD, [&](Index* ix) -> int {
+    return on_index_host(h, what, WHOLE_CLOUD, [&](Index* ix, Staged& stage) -> int {
         int st;
         if ((st = check_fpfh_args(what, normals, radius, opt_rows, m, flags, fpfh)) != PCPX_OK) return st;
         const u64 rows = ix->n_in, out_rows = opt_rows ? m : rows;
@@ -352,25 +339,20 @@ int pcpx_fpfh_self(pcpx_index* h, const float* normals, float radius, const uint
             if (out_rows) std::memset(fpfh, 0, out_rows * NF * sizeof(float));
             return PCPX_OK;
         }
-        DevBuf dn(ix->pool), dr(ix->pool), df(ix->pool), ds(ix->pool), dp(ix->pool);
-        if ((st = dn.alloc(rows * 3 * sizeof(float))) != PCPX_OK) return st;
-        if (opt_rows && m && (st = dr.alloc(m * sizeof(u32))) != PCPX_OK) return st;
-        if (out_rows && (st = df.alloc(out_rows * NF * sizeof(float))) != PCPX_OK) return st;
-        if (opt_spfh && (st = ds.alloc(rows * NF * sizeof(float))) != PCPX_OK) return st;
-        if (opt_pairs && (st = dp.alloc(rows * sizeof(u32))) != PCPX_OK) return st;
-        if ((st = upload_pageable(dn.p, normals, rows * 3 * sizeof(float), ix->stream)) != PCPX_OK) return st;
-        if (dr.p && (st = upload_pageable(dr.p, opt_rows, m * sizeof(u32), ix->stream)) != PCPX_OK) return st;
+        const float* dn = stage.upload(normals, rows * 3 * sizeof(float));
+        const u32* dr = stage.upload(opt_rows, m * sizeof(u32));  // (null for m = 0)
+        float* df = stage.alloc<float>(out_rows * NF * sizeof(float));
+        float* ds = stage.alloc_for(opt_spfh, rows * NF * sizeof(float));
+        u32* dp = stage.alloc_for(opt_pairs, rows * sizeof(u32));
+        if ((st = stage.st) != PCPX_OK) return st;
         {
             ProfileScope prof(*ix, PCPX_K_RANGE);
-            if ((st = fpfh_self(*ix, dn.as<float>(), radius, opt_rows != nullptr, dr.as<u32>(), m, df.as<float>(), ds.as<float>(), dp.as<u32>())) !=
-                PCPX_OK)
-                return st;
+            if ((st = fpfh_self(*ix, dn, radius, opt_rows != nullptr, dr, m, df, ds, dp)) != PCPX_OK) return st;
         }
-        if (out_rows) PCPX_HIP(hipMemcpyAsync(fpfh, df.p, out_rows * NF * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
-        if (opt_spfh) PCPX_HIP(hipMemcpyAsync(opt_spfh, ds.p, rows * NF * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
-        if (opt_pairs) PCPX_HIP(hipMemcpyAsync(opt_pairs, dp.p, rows * sizeof(u32), hipMemcpyDeviceToHost, ix->stream));
-        PCPX_HIP(hipStreamSynchronize(ix->stream));
-        return PCPX_OK;
+        if (out_rows) stage.download(fpfh, df, out_rows * NF * sizeof(float));
+        stage.download_opt(opt_spfh, ds, rows * NF * sizeof(float));
+        stage.download_opt(opt_pairs, dp, rows * sizeof(u32));
+        return stage.wait();
     });
 }
 

@@ -48,6 +48,15 @@ struct NodeBox4 {
     NodeBox c[W];
 };
 
+// The normals of a leaf's eight points by curve position, SoA like the leaf record itself (Leaf, pcpx_internal.h): one 96-byte
+// scalar load per leaf, beside its coordinate record (pcpx_segment.hip, pcpx_descriptors.hip).
+struct Normals8 {
+    float x[LEAF];
+    float y[LEAF];
+    float z[LEAF];
+};
+static_assert(sizeof(Normals8) == 12 * LEAF, "normal record must be dense");
+
 // The four child boxes of a node as two 64-byte scalar loads.  (From load_const hipcc fetches only the seven used words of
 // each box -- x4 + x2 + x1: twelve SMEM instructions per expansion, and the scalar side of the query kernels is as loaded
 // as their vector side.)  The wait is part of the statement: the compiler does not count loads it cannot see.

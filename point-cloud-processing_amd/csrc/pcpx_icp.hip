@@ -35,7 +35,6 @@ constexpr bool ICP_PREVIOUS_START = true;
 constexpr u32 ICP_SLOTS = 64, ICP_SLOT_STRIDE = 32;
 constexpr u32 PLANE_TERMS = PLANE_A_TERMS + PLANE_B_TERMS + 2, PLANE_STRIDE = 32;  // A, b, sum rho^2, rows
 
-inline u32 blocks_of(u64 n, u32 per) { return static_cast<u32>((n + per - 1) / per); }
 
 // The words of a loop on the device.  done: every kernel of a later round reads it first and returns.  fit_count: the number of
 // correspondences the fit's kernels see -- m while the loop runs, 0 once it has stopped, so that they pass over nothing and stay

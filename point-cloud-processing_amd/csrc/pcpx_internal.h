@@ -673,6 +673,12 @@ inline int check_slice(const char* what, u64 sorted_first)
     set_error("%s: sorted_first must be a multiple of %d", what, GROUP);
     return PCPX_ERR_INVALID;
 }
+inline int check_radius(const char* what, float radius)
+{
+    if (radius >= 0.f) return PCPX_OK;  // (false for NaN)
+    set_error("%s: the radius must be >= 0 (got %g)", what, static_cast<double>(radius));
+    return PCPX_ERR_INVALID;
+}
 // the index's own points as queries
 inline QueryView self_view(const Index& ix) { return QueryView{nullptr, nullptr, nullptr, nullptr, nullptr, static_cast<u32>(ix.n)}; }
 // calls that need a neighbourhood for every input point

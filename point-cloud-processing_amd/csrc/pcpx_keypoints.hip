@@ -4,8 +4,7 @@
 // scores leaf by leaf the way it reads their coordinates.  Unlike pcpx_subsample.hip it needs no rounds: the answer for a point
 // depends only on the scores in its own sphere, which nothing writes during the launch.  So it is one launch, a leaf's eight
 // scores are one scalar load, and a beaten lane goes idle at once.
-#include "pcpx_device.h"
-#include "pcpx_scan.h"
+#include "pcpx_keep.h"
 #include "pcpx_keypoints.h"
 
 namespace pcpx {
@@ -92,32 +91,17 @@ __global__ __launch_bounds__(KP_BLOCK) void k_iss_score(u32 rows, const float* _
     saliency[i] = s;
 }
 
-// ---- the kept rows, ascending: the exclusive scan of the keep mask is a kept row's place in the list (as pcpx_subsample.hip) --------
-struct IsKept {
-    const uint8_t* keep;
-    __device__ u32 operator()(u32 i) const { return keep[i] ? 1u : 0u; }
-};
-__global__ __launch_bounds__(KP_BLOCK) void k_maxima_compact(const uint8_t* __restrict__ keep, u32 n, const u32* __restrict__ place,
-                                                             u32* __restrict__ kept_rows)
-{
-    const u32 i = blockIdx.x * KP_BLOCK + threadIdx.x;
-    if (i < n && keep[i]) kept_rows[place[i]] = i;
-}
-
-inline u32 blocks_of(u64 n, u32 per) { return static_cast<u32>((n + per - 1) / per); }
-inline size_t padded(u64 bytes) { return (bytes + 255) / 256 * 256; }
-
-// scratch of the local maxima: the score records (one word per leaf slot; the scan's places, one word per input row, take their
-// room once the walk is done) and the scan's tile sums
+// Where the local maxima's arrays lie in the handle's scratch, taken from the caller's Carve (the ISS call keeps its own arrays
+// below them): the score records (one word per leaf slot; the scan's places, one word per input row, take their room once the walk
+// is done) and the scan's tile sums.  The caller ensures the scratch for the whole Carve before anything is enqueued.
 struct MaximaScratch {
-    size_t words_bytes, sums_bytes;
-    explicit MaximaScratch(const Index& ix)
+    size_t words_at, sums_at;
+    MaximaScratch(Carve& c, const Index& ix)
     {
         const u64 npos = static_cast<u64>(ix.nleaves) * LEAF, rows = ix.n_in;
-        words_bytes = padded((npos > rows ? npos : rows) * sizeof(u32));
-        sums_bytes = padded((scan_tiles(rows) + 1ull) * sizeof(u32));
+        words_at = c.take((npos > rows ? npos : rows) * sizeof(u32));
+        sums_at = c.take((scan_tiles(rows) + 1ull) * sizeof(u32));
     }
-    size_t bytes() const { return words_bytes + sums_bytes; }
 };
 
 int check_maxima_args(const char* what, float radius, const char* radius_name, u32 flags, const void* keep)
@@ -143,22 +127,19 @@ int check_not_nan(const char* what, float v, const char* name)
     return PCPX_ERR_INVALID;
 }
 
-// Everything is enqueued on the handle's stream.  Scratch of the handle from byte `at` on (the ISS call keeps its arrays below).
-int local_maxima_self(Index& ix, size_t at, const float* d_score, float radius, float min_score, u32 min_neighbours, uint8_t* d_keep,
-                      u32* d_kept_rows, u64* d_kept_count)
+// Everything is enqueued on the handle's stream.  Scratch of the handle: `at`, which the caller has ensured (no row: none needed).
+int local_maxima_at(Index& ix, const MaximaScratch& at, const float* d_score, float radius, float min_score, u32 min_neighbours, uint8_t* d_keep,
+                    u32* d_kept_rows, u64* d_kept_count)
 {
-    int st;
     hipStream_t s = ix.stream;
     const u64 rows = ix.n_in, n = ix.n;
     if (rows == 0) {
         if (d_kept_count) PCPX_HIP(hipMemsetAsync(d_kept_count, 0, sizeof(u64), s));
         return PCPX_OK;
     }
-    const MaximaScratch need(ix);
-    if ((st = ensure_scratch(ix, at + need.bytes())) != PCPX_OK) return st;
-    char* base = static_cast<char*>(ix.d_scratch) + at;
-    Scores8* srec = reinterpret_cast<Scores8*>(base);
-    u32* sums = reinterpret_cast<u32*>(base + need.words_bytes);
+    char* base = static_cast<char*>(ix.d_scratch);
+    Scores8* srec = reinterpret_cast<Scores8*>(base + at.words_at);
+    u32* sums = reinterpret_cast<u32*>(base + at.sums_at);
     if (n > 0) {
         const TreeView t = ix.view();
         const u64 npos = static_cast<u64>(ix.nleaves) * LEAF;  // >= n
@@ -170,31 +151,37 @@ int local_maxima_self(Index& ix, size_t at, const float* d_score, float radius, 
     } else {
         PCPX_HIP(hipMemsetAsync(d_keep, 0, rows * sizeof(uint8_t), s));  // every point lies outside the voxel grid
     }
-    if (d_kept_rows || d_kept_count) {
-        u32* place = d_kept_rows ? reinterpret_cast<u32*>(base) : nullptr;  // (the records are free by now); place[i] = kept rows among [0, i)
-        if ((st = exclusive_scan(IsKept{d_keep}, rows, sums, place, d_kept_count, s)) != PCPX_OK) return st;
-        if (d_kept_rows) k_maxima_compact<<<blocks_of(rows, KP_BLOCK), KP_BLOCK, 0, s>>>(d_keep, static_cast<u32>(rows), place, d_kept_rows);
-        PCPX_HIP(hipGetLastError());
-    }
-    return PCPX_OK;
+    // (the records are free by now: the scan's places)
+    return count_and_compact_kept(d_keep, rows, reinterpret_cast<u32*>(srec), sums, d_kept_rows, d_kept_count, s);
 }
 
-// The features form at the salient radius into the handle's scratch, the saliency, its local maxima at the other radius.
+int local_maxima_self(Index& ix, const float* d_score, float radius, float min_score, u32 min_neighbours, uint8_t* d_keep, u32* d_kept_rows,
+                      u64* d_kept_count)
+{
+    Carve c;
+    const MaximaScratch at(c, ix);
+    if (const int st = ix.n_in ? ensure_scratch(ix, c.bytes()) : PCPX_OK) return st;
+    return local_maxima_at(ix, at, d_score, radius, min_score, min_neighbours, d_keep, d_kept_rows, d_kept_count);
+}
+
+// The features form at the salient radius into the handle's scratch, the saliency, its local maxima at the other radius.  One Carve
+// for its own arrays and the maxima's, ensured once: nothing moves under the arrays already written.
 int iss_keypoints_self(Index& ix, float salient_radius, float non_max_radius, float gamma21, float gamma32, u32 min_neighbours, uint8_t* d_keep,
                        u32* d_kept_rows, u64* d_kept_count, float* d_saliency)
 {
     int st;
     hipStream_t s = ix.stream;
     const u64 rows = ix.n_in, n = ix.n;
-    if (rows == 0) return local_maxima_self(ix, 0, nullptr, non_max_radius, 0.f, min_neighbours, d_keep, d_kept_rows, d_kept_count);
-    const size_t evals_bytes = padded(rows * 3 * sizeof(float)), count_bytes = padded(rows * sizeof(u32));
-    const size_t saliency_bytes = d_saliency ? 0 : padded(rows * sizeof(float));
-    const size_t at = evals_bytes + count_bytes + saliency_bytes;
-    if ((st = ensure_scratch(ix, at + MaximaScratch(ix).bytes())) != PCPX_OK) return st;
+    if (rows == 0) return local_maxima_self(ix, nullptr, non_max_radius, 0.f, min_neighbours, d_keep, d_kept_rows, d_kept_count);
+    Carve c;
+    const size_t evals_at = c.take(rows * 3 * sizeof(float)), count_at = c.take(rows * sizeof(u32));
+    const size_t saliency_at = d_saliency ? 0 : c.take(rows * sizeof(float));
+    const MaximaScratch maxima(c, ix);
+    if ((st = ensure_scratch(ix, c.bytes())) != PCPX_OK) return st;
     char* base = static_cast<char*>(ix.d_scratch);
-    float* evals = reinterpret_cast<float*>(base);
-    u32* count = reinterpret_cast<u32*>(base + evals_bytes);
-    if (!d_saliency) d_saliency = reinterpret_cast<float*>(base + evals_bytes + count_bytes);
+    float* evals = reinterpret_cast<float*>(base + evals_at);
+    u32* count = reinterpret_cast<u32*>(base + count_at);
+    if (!d_saliency) d_saliency = reinterpret_cast<float*>(base + saliency_at);
     if (n != rows) PCPX_HIP(hipMemsetAsync(count, 0, rows * sizeof(u32), s));  // the rows of the points outside the voxel grid
     if (n > 0) {
         if ((st = launch_range_features(ix, self_view(ix), true, 0, (n + GROUP - 1) / GROUP, salient_radius, nullptr, evals, nullptr, nullptr, nullptr,
@@ -203,8 +190,8 @@ int iss_keypoints_self(Index& ix, float salient_radius, float non_max_radius, fl
     }
     k_iss_score<<<blocks_of(rows, KP_BLOCK), KP_BLOCK, 0, s>>>(static_cast<u32>(rows), evals, count, gamma21, gamma32, d_saliency);
     PCPX_HIP(hipGetLastError());
-    return local_maxima_self(ix, at, d_saliency, non_max_radius, -std::numeric_limits<float>::infinity(), min_neighbours, d_keep, d_kept_rows,
-                             d_kept_count);
+    return local_maxima_at(ix, maxima, d_saliency, non_max_radius, -std::numeric_limits<float>::infinity(), min_neighbours, d_keep, d_kept_rows,
+                           d_kept_count);
 }
 
 // One interval of the PCPX_K_RANGE family for the whole call: what the call launches through other modules books nothing of its own.
@@ -217,38 +204,6 @@ int booked_as_one_range_interval(Index& ix, Body&& body)
     const int st = body();
     ix.profiling = profiling;
     return st;
-}
-
-// keep, kept rows and count (and one more array of n_in floats) back to the host after `run` has filled their device blocks
-struct KeptHost {
-    uint8_t* keep;
-    u32* kept_rows;
-    u64* kept_count;
-    float* saliency;
-};
-template <class Run>
-int kept_to_host(Index* ix, const KeptHost& out, Run&& run)
-{
-    int st;
-    const u64 rows = ix->n_in;
-    const bool want_count = out.kept_rows || out.kept_count;
-    DevBuf dk(ix->pool), dr(ix->pool), dt(ix->pool), ds(ix->pool);
-    if ((st = dk.alloc(rows * sizeof(uint8_t))) != PCPX_OK) return st;
-    if (out.kept_rows && (st = dr.alloc(rows * sizeof(u32))) != PCPX_OK) return st;
-    if (want_count && (st = dt.alloc(sizeof(u64))) != PCPX_OK) return st;
-    if (out.saliency && (st = ds.alloc(rows * sizeof(float))) != PCPX_OK) return st;
-    if ((st = run(KeptHost{dk.as<uint8_t>(), dr.as<u32>(), dt.as<u64>(), ds.as<float>()})) != PCPX_OK) return st;
-    u64 count = 0;
-    PCPX_HIP(hipMemcpyAsync(out.keep, dk.p, rows * sizeof(uint8_t), hipMemcpyDeviceToHost, ix->stream));
-    if (out.saliency) PCPX_HIP(hipMemcpyAsync(out.saliency, ds.p, rows * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
-    if (want_count) PCPX_HIP(hipMemcpyAsync(&count, dt.p, sizeof(u64), hipMemcpyDeviceToHost, ix->stream));
-    PCPX_HIP(hipStreamSynchronize(ix->stream));
-    if (out.kept_count) *out.kept_count = count;
-    if (out.kept_rows && count) {  // (count <= rows)
-        PCPX_HIP(hipMemcpyAsync(out.kept_rows, dr.p, count * sizeof(u32), hipMemcpyDeviceToHost, ix->stream));
-        PCPX_HIP(hipStreamSynchronize(ix->stream));
-    }
-    return PCPX_OK;
 }
 
 int check_local_maxima(const char* what, const float* score, float radius, float min_score, u32 flags, const void* keep)
@@ -287,7 +242,7 @@ int pcpx_local_maxima_self_dev(pcpx_index* h, const float* d_score, float radius
         int st;
         if ((st = check_local_maxima(what, d_score, radius, min_score, flags, d_keep)) != PCPX_OK) return st;
         return booked_as_one_range_interval(*ix, [&] {
-            return local_maxima_self(*ix, 0, d_score, radius, min_score, min_neighbours, d_keep, d_opt_kept_rows, d_opt_kept_count);
+            return local_maxima_self(*ix, d_score, radius, min_score, min_neighbours, d_keep, d_opt_kept_rows, d_opt_kept_count);
         });
     });
 }
@@ -296,20 +251,21 @@ int pcpx_local_maxima_self(pcpx_index* h, const float* score, float radius, floa
                            uint8_t* keep, uint32_t* opt_kept_rows, uint64_t* opt_kept_count)
 {
     static const char* what = "pcpx_local_maxima_self";
-    return on_index(h, what, WHOLE_CLOUD, [&](Index* ix) -> int {
+    return on_index_host(h, what, WHOLE_CLOUD, [&](Index* ix, Staged& stage) -> int {
         int st;
         if ((st = check_local_maxima(what, score, radius, min_score, flags, keep)) != PCPX_OK) return st;
         if (opt_kept_count) *opt_kept_count = 0;
         const u64 rows = ix->n_in;
         if (rows == 0) return PCPX_OK;
-        DevBuf dscore(ix->pool);
-        if ((st = dscore.alloc(rows * sizeof(float))) != PCPX_OK) return st;
-        PCPX_HIP(hipMemcpyAsync(dscore.p, score, rows * sizeof(float), hipMemcpyHostToDevice, ix->stream));
-        return kept_to_host(ix, KeptHost{keep, opt_kept_rows, opt_kept_count, nullptr}, [&](const KeptHost& d) {
-            return booked_as_one_range_interval(*ix, [&] {
-                return local_maxima_self(*ix, 0, dscore.as<float>(), radius, min_score, min_neighbours, d.keep, d.kept_rows, d.kept_count);
-            });
-        });
+        const float* dscore = stage.upload(score, rows * sizeof(float), true);  // (plain: measured, pcpx_stage.h)
+        uint8_t* dk = stage.alloc<uint8_t>(rows * sizeof(uint8_t));
+        u32* dr = stage.alloc_for(opt_kept_rows, rows * sizeof(u32));
+        u64* dt = opt_kept_rows || opt_kept_count ? stage.alloc<u64>(sizeof(u64)) : nullptr;
+        if ((st = stage.st) != PCPX_OK) return st;
+        st = booked_as_one_range_interval(*ix, [&] { return local_maxima_self(*ix, dscore, radius, min_score, min_neighbours, dk, dr, dt); });
+        if (st != PCPX_OK) return st;
+        stage.download(keep, dk, rows * sizeof(uint8_t));
+        return download_kept(stage, dt, dr, opt_kept_count, opt_kept_rows);
     });
 }
 
@@ -331,17 +287,24 @@ int pcpx_iss_keypoints_self(pcpx_index* h, float salient_radius, float non_max_r
                             uint32_t flags, uint8_t* keep, uint32_t* opt_kept_rows, uint64_t* opt_kept_count, float* opt_saliency)
 {
     static const char* what = "pcpx_iss_keypoints_self";
-    return on_index(h, what, WHOLE_CLOUD, [&](Index* ix) -> int {
+    return on_index_host(h, what, WHOLE_CLOUD, [&](Index* ix, Staged& stage) -> int {
         int st;
         if ((st = check_iss(what, salient_radius, non_max_radius, gamma21, gamma32, flags, keep)) != PCPX_OK) return st;
         if (opt_kept_count) *opt_kept_count = 0;
-        if (ix->n_in == 0) return PCPX_OK;
-        return kept_to_host(ix, KeptHost{keep, opt_kept_rows, opt_kept_count, opt_saliency}, [&](const KeptHost& d) {
-            return booked_as_one_range_interval(*ix, [&] {
-                return iss_keypoints_self(*ix, salient_radius, non_max_radius, gamma21, gamma32, min_neighbours, d.keep, d.kept_rows, d.kept_count,
-                                          d.saliency);
-            });
+        const u64 rows = ix->n_in;
+        if (rows == 0) return PCPX_OK;
+        uint8_t* dk = stage.alloc<uint8_t>(rows * sizeof(uint8_t));
+        u32* dr = stage.alloc_for(opt_kept_rows, rows * sizeof(u32));
+        u64* dt = opt_kept_rows || opt_kept_count ? stage.alloc<u64>(sizeof(u64)) : nullptr;
+        float* ds = stage.alloc_for(opt_saliency, rows * sizeof(float));
+        if ((st = stage.st) != PCPX_OK) return st;
+        st = booked_as_one_range_interval(*ix, [&] {
+            return iss_keypoints_self(*ix, salient_radius, non_max_radius, gamma21, gamma32, min_neighbours, dk, dr, dt, ds);
         });
+        if (st != PCPX_OK) return st;
+        stage.download(keep, dk, rows * sizeof(uint8_t));
+        stage.download_opt(opt_saliency, ds, rows * sizeof(float));
+        return download_kept(stage, dt, dr, opt_kept_count, opt_kept_rows);
     });
 }
 

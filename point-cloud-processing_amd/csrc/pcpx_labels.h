@@ -6,6 +6,7 @@
 
 #include "pcpx_device.h"
 #include "pcpx_scan.h"
+#include "pcpx_stage.h"
 #include "pcpx_unionfind.h"
 
 namespace pcpx {
@@ -82,8 +83,6 @@ __global__ __launch_bounds__(CL_BLOCK) void k_cluster_compact(u32* __restrict__ 
     const u32 l = labels[i];
     if (l != NOT_CORE) labels[i] = rank[l];
 }
-
-inline u32 blocks_of(u64 n, u32 per) { return static_cast<u32>((n + per - 1) / per); }
 
 // The tail of a labelling call: the count of representatives among `rows` label rows into *d_count (may be null) and, compact, the
 // labels renumbered 0 ... C-1 in the order of the representatives.  rank: `rows` words (used only when compact); sums: the scan's

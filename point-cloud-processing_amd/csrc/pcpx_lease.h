@@ -5,25 +5,11 @@
 #ifndef PCPX_LEASE_H
 #define PCPX_LEASE_H
 
-#include "pcpx_internal.h"
+#include "pcpx_stage.h"
 
-#include <deque>
 #include <vector>
 
 namespace pcpx {
-
-// Where everything lies in the scratch of a call: byte offsets from its start, each a multiple of 256.
-inline size_t padded(u64 bytes) { return (bytes + 255) / 256 * 256; }
-struct Carve {
-    size_t at = 0;
-    size_t take(u64 bytes)
-    {
-        const size_t here = at;
-        at += padded(bytes);
-        return here;
-    }
-    size_t bytes() const { return at; }
-};
 
 // A block of the device's pool goes back to the pool when the host knows that nothing queued reads it.  A _dev call returns before
 // that, so it leaves the block here with an event recorded behind its last kernel; the next such call on the device gives
@@ -113,55 +99,26 @@ int on_leased(int device, const char* what, void* stream, size_t bytes, Body&& b
     });
 }
 
-// A host-pointer call on the device: a stream of the pool, the caller's arrays in blocks of the device's pool, blocks for the
-// outputs, the scratch, and the wait.  A failed step makes the later ones do nothing and stays in `st`.  The blocks go back to the
-// pool when the call ends, after the stream has been waited on (a failed call waits in the lease's destructor).
-struct HostCall {
-    DevPool& pool;
+// A host-pointer call on the device: the staging (pcpx_stage.h) on a stream of the pool, and the scratch.  Destruction order, which
+// the order of the bases and the member fixes: the lease goes first (a failed call that holds a block waits for the stream there),
+// then the staging (it waits if the call did not reach a successful wait(), and its blocks go back to the pool), and the pooled
+// stream goes back last, when nothing queued on it is left.
+struct HostCallStream {
     PooledStream ps;
-    std::deque<DevBuf> blocks;
-    ScratchLease lease;  // (last: the first to go)
-    hipStream_t s = nullptr;
-    int st = PCPX_OK;
-    HostCall(DeviceShared& sh, int device) : pool(sh.pool), lease(sh, device, nullptr) {}
+};
+struct HostCall : HostCallStream, Staged {
+    ScratchLease lease;
+    HostCall(DeviceShared& sh, int device) : Staged(sh.pool, nullptr), lease(sh, device, nullptr) {}
     int begin()
     {
         PCPX_HIP(pooled_stream_get(&ps.s));
         s = lease.stream = ps.s;
         return PCPX_OK;
     }
-    // `bytes` of device memory; null for none
-    void* alloc(size_t bytes)
-    {
-        if (st != PCPX_OK || !bytes) return nullptr;
-        blocks.emplace_back(pool);
-        st = blocks.back().alloc(bytes);
-        return blocks.back().p;
-    }
-    template <class T>
-    T* alloc(size_t bytes) { return static_cast<T*>(alloc(bytes)); }
-    // this host array of this many bytes on the device, or null when there is none
-    template <class T>
-    const T* upload(const T* host, size_t bytes)
-    {
-        void* d = host ? alloc(bytes) : nullptr;
-        if (d && st == PCPX_OK) st = upload_pageable(d, host, bytes, s);
-        return static_cast<const T*>(d);
-    }
     char* scratch(size_t bytes)
     {
         if (st == PCPX_OK) st = lease.take(bytes);
         return static_cast<char*>(lease.p);
-    }
-    int download(void* host, const void* d, size_t bytes)
-    {
-        PCPX_HIP(hipMemcpyAsync(host, d, bytes, hipMemcpyDeviceToHost, s));
-        return PCPX_OK;
-    }
-    int wait()
-    {
-        PCPX_HIP(hipStreamSynchronize(s));
-        return PCPX_OK;
     }
 };
 

@@ -45,7 +45,6 @@ inline u32 width_for(u32 dims)
     return 0;
 }
 
-inline u32 blocks_of(u64 n, u32 per) { return static_cast<u32>((n + per - 1) / per); }
 
 struct Split {
     u32 segments = 0;

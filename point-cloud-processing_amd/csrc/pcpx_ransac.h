@@ -21,7 +21,6 @@ constexpr u32 FIT_TERMS = 16;  // the doubles a block's partial sums of a fit ar
 // the scratch of a fit whose state is `state` doubles: the blocks' partial sums, then the state
 constexpr size_t fit_bytes(u32 state) { return (static_cast<size_t>(FIT_BLOCKS) * FIT_TERMS + state) * sizeof(double); }
 
-inline u32 blocks_of(u64 n, u32 per) { return static_cast<u32>((n + per - 1) / per); }
 
 // The plan: a wave is 64 hypotheses on one segment of the records, a call should be several rounds of what the device holds
 // (PLAN_TARGET_WAVES), a segment is never shorter than PLAN_MIN_SEGMENT_ROWS (a wave's prologue -- three gathers and what it makes

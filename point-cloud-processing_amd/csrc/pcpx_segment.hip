@@ -13,14 +13,6 @@ namespace {
 
 static_assert(NOT_CORE == PCPX_SEGMENT_NOISE, "a non-smooth position's parent word is the noise label");
 
-// The normals of a leaf's eight points by curve position, SoA like the leaf record itself: one 96-byte scalar load per leaf.
-struct Normals8 {
-    float x[LEAF];
-    float y[LEAF];
-    float z[LEAF];
-};
-static_assert(sizeof(Normals8) == 12 * LEAF, "normal record must be dense");
-
 // t = (ax bx + ay by) + az bz, every product and both sums rounded (no FMA: pcpx_device.h turns contraction off); |t| >= min_cos,
 // or t >= min_cos where the normals' signs matter.  A NaN t fails either test.  Symmetric: every product commutes exactly.
 template <bool ORIENTED>
@@ -173,10 +165,7 @@ constexpr u32 SEGMENT_FLAGS = PCPX_SEGMENT_COMPACT | PCPX_SEGMENT_ORIENTED;
 int check_segment_args(const char* what, const void* normals, const void* curvature, float radius, float min_cos, float max_curvature,
                        u32 flags, const void* labels)
 {
-    if (!(radius >= 0.f)) {  // (false for NaN)
-        set_error("%s: the radius must be >= 0 (got %g)", what, static_cast<double>(radius));
-        return PCPX_ERR_INVALID;
-    }
+    if (const int st = check_radius(what, radius)) return st;
     if (min_cos != min_cos) {
         set_error("%s: min_cos is NaN", what);
         return PCPX_ERR_INVALID;
@@ -228,15 +217,16 @@ int segment_self(Index& ix, const float* d_normals, const float* d_curvature, fl
     }
     const u64 npos = static_cast<u64>(ix.nleaves) * LEAF;  // >= n
     const u32 ntiles = scan_tiles(rows);
-    auto padded = [](u64 bytes) { return (bytes + 255) / 256 * 256; };
-    const size_t words_bytes = padded((npos > rows ? npos : rows) * sizeof(u32)), sums_bytes = padded((ntiles + 1) * sizeof(u32)),
-                 nrec_bytes = padded((ix.nleaves ? ix.nleaves : 1u) * sizeof(Normals8));
-    if ((st = ensure_scratch(ix, 2 * words_bytes + sums_bytes + nrec_bytes)) != PCPX_OK) return st;
+    Carve c;
+    const u64 words = npos > rows ? npos : rows;
+    const size_t parent_at = c.take(words * sizeof(u32)), aux_at = c.take(words * sizeof(u32)), sums_at = c.take((ntiles + 1ull) * sizeof(u32)),
+                 nrec_at = c.take((ix.nleaves ? ix.nleaves : 1u) * sizeof(Normals8));
+    if ((st = ensure_scratch(ix, c.bytes())) != PCPX_OK) return st;
     char* base = static_cast<char*>(ix.d_scratch);
-    u32* parent = reinterpret_cast<u32*>(base);
-    u32* aux = reinterpret_cast<u32*>(base + words_bytes);
-    u32* sums = reinterpret_cast<u32*>(base + 2 * words_bytes);
-    Normals8* nrec = reinterpret_cast<Normals8*>(base + 2 * words_bytes + sums_bytes);
+    u32* parent = reinterpret_cast<u32*>(base + parent_at);
+    u32* aux = reinterpret_cast<u32*>(base + aux_at);
+    u32* sums = reinterpret_cast<u32*>(base + sums_at);
+    Normals8* nrec = reinterpret_cast<Normals8*>(base + nrec_at);
     if (n != rows) {  // the rows of the points outside the voxel grid: noise, not smooth
         PCPX_HIP(hipMemsetAsync(d_labels, 0xFF, rows * sizeof(u32), s));
         if (d_smooth) PCPX_HIP(hipMemsetAsync(d_smooth, 0, rows * sizeof(uint8_t), s));
@@ -286,28 +276,24 @@ int pcpx_segment_self(pcpx_index* h, const float* normals, const float* opt_curv
                       uint32_t min_size, uint32_t flags, uint32_t* labels, uint8_t* opt_smooth, uint64_t* opt_segment_count)
 {
     static const char* what = "pcpx_segment_self";
-    return on_index(h, what, WHOLE_CLOUD, [&](Index* ix) -> int {
+    return on_index_host(h, what, WHOLE_CLOUD, [&](Index* ix, Staged& stage) -> int {
         int st;
         if ((st = check_segment_args(what, normals, opt_curvature, radius, min_cos, max_curvature, flags, labels)) != PCPX_OK) return st;
         if (opt_segment_count) *opt_segment_count = 0;
         const u64 rows = ix->n_in;
         if (rows == 0) return PCPX_OK;
-        DevBuf dn(ix->pool), dk(ix->pool), dl(ix->pool), ds(ix->pool), dt(ix->pool);
-        if ((st = dn.alloc(rows * 3 * sizeof(float))) != PCPX_OK) return st;
-        if (opt_curvature && (st = dk.alloc(rows * sizeof(float))) != PCPX_OK) return st;
-        if ((st = dl.alloc(rows * sizeof(u32))) != PCPX_OK) return st;
-        if (opt_smooth && (st = ds.alloc(rows * sizeof(uint8_t))) != PCPX_OK) return st;
-        if (opt_segment_count && (st = dt.alloc(sizeof(u64))) != PCPX_OK) return st;
-        if ((st = upload_pageable(dn.p, normals, rows * 3 * sizeof(float), ix->stream)) != PCPX_OK) return st;
-        if (opt_curvature && (st = upload_pageable(dk.p, opt_curvature, rows * sizeof(float), ix->stream)) != PCPX_OK) return st;
-        if ((st = segment_self(*ix, dn.as<float>(), dk.as<float>(), radius, min_cos, max_curvature, min_size, flags, dl.as<u32>(),
-                               ds.as<uint8_t>(), dt.as<u64>())) != PCPX_OK)
+        const float* dn = stage.upload(normals, rows * 3 * sizeof(float));
+        const float* dk = stage.upload(opt_curvature, rows * sizeof(float));
+        u32* dl = stage.alloc<u32>(rows * sizeof(u32));
+        uint8_t* ds = stage.alloc_for(opt_smooth, rows * sizeof(uint8_t));
+        u64* dt = stage.alloc_for(opt_segment_count, sizeof(u64));
+        if ((st = stage.st) != PCPX_OK ||
+            (st = segment_self(*ix, dn, dk, radius, min_cos, max_curvature, min_size, flags, dl, ds, dt)) != PCPX_OK)
             return st;
-        PCPX_HIP(hipMemcpyAsync(labels, dl.p, rows * sizeof(u32), hipMemcpyDeviceToHost, ix->stream));
-        if (opt_smooth) PCPX_HIP(hipMemcpyAsync(opt_smooth, ds.p, rows * sizeof(uint8_t), hipMemcpyDeviceToHost, ix->stream));
-        if (opt_segment_count) PCPX_HIP(hipMemcpyAsync(opt_segment_count, dt.p, sizeof(u64), hipMemcpyDeviceToHost, ix->stream));
-        PCPX_HIP(hipStreamSynchronize(ix->stream));
-        return PCPX_OK;
+        stage.download(labels, dl, rows * sizeof(u32));
+        stage.download_opt(opt_smooth, ds, rows * sizeof(uint8_t));
+        stage.download_opt(opt_segment_count, dt, sizeof(u64));
+        return stage.wait();
     });
 }
 

@@ -18,8 +18,7 @@
 //     launches before it: every round decides at least that point.  Against the synchronous form (every lane reads the words as they
 //     were when the round began: tests/subsample_model.py) a round here reads words that are at least as far, so by induction over
 //     the rounds it has decided at least what the synchronous form has: never more rounds than that.
-#include "pcpx_device.h"
-#include "pcpx_scan.h"
+#include "pcpx_keep.h"
 #include "pcpx_subsample.h"
 
 namespace pcpx {
@@ -138,26 +137,9 @@ __global__ __launch_bounds__(SS_BLOCK) void k_subsample_rows(TreeView t, const u
     keep[t.leaves[p / LEAF].id[p % LEAF]] = state[p] == KEPT ? 1 : 0;
 }
 
-// ---- the kept rows, ascending: the exclusive scan of the keep mask is a kept row's place in the list ---------------------------------
-struct IsKept {
-    const uint8_t* keep;
-    __device__ u32 operator()(u32 i) const { return keep[i] ? 1u : 0u; }
-};
-__global__ __launch_bounds__(SS_BLOCK) void k_subsample_compact(const uint8_t* __restrict__ keep, u32 n, const u32* __restrict__ place,
-                                                                u32* __restrict__ kept_rows)
-{
-    const u32 i = blockIdx.x * SS_BLOCK + threadIdx.x;
-    if (i < n && keep[i]) kept_rows[place[i]] = i;
-}
-
-inline u32 blocks_of(u64 n, u32 per) { return static_cast<u32>((n + per - 1) / per); }
-
 int check_subsample_args(const char* what, float radius, u32 flags, const void* keep)
 {
-    if (!(radius >= 0.f)) {  // (false for NaN)
-        set_error("%s: the radius must be >= 0 (got %g)", what, static_cast<double>(radius));
-        return PCPX_ERR_INVALID;
-    }
+    if (const int st = check_radius(what, radius)) return st;
     if (flags != 0u) {
         set_error("%s: unknown flag bits 0x%x", what, flags);
         return PCPX_ERR_INVALID;
@@ -187,12 +169,14 @@ int subsample_self(Index& ix, float radius, u32 seed, uint8_t* d_keep, u32* d_ow
     }
     const u64 npos = static_cast<u64>(ix.nleaves) * LEAF;  // >= n
     const u32 ntiles = scan_tiles(rows);
-    auto padded = [](u64 words) { return (words * sizeof(u32) + 255) / 256 * 256; };
-    const size_t state_bytes = padded(npos > rows ? npos : rows), sums_bytes = padded(ntiles + 1);
-    if ((st = ensure_scratch(ix, state_bytes + sums_bytes + padded(1))) != PCPX_OK) return st;
-    u32* state = static_cast<u32*>(ix.d_scratch);
-    u32* sums = reinterpret_cast<u32*>(static_cast<char*>(ix.d_scratch) + state_bytes);
-    u32* decided = reinterpret_cast<u32*>(static_cast<char*>(ix.d_scratch) + state_bytes + sums_bytes);
+    Carve c;
+    const size_t state_at = c.take((npos > rows ? npos : rows) * sizeof(u32)), sums_at = c.take((ntiles + 1ull) * sizeof(u32)),
+                 decided_at = c.take(sizeof(u32));
+    if ((st = ensure_scratch(ix, c.bytes())) != PCPX_OK) return st;
+    char* base = static_cast<char*>(ix.d_scratch);
+    u32* state = reinterpret_cast<u32*>(base + state_at);
+    u32* sums = reinterpret_cast<u32*>(base + sums_at);
+    u32* decided = reinterpret_cast<u32*>(base + decided_at);
     if (n != rows) {  // the rows of the points outside the voxel grid: dropped, no owner
         PCPX_HIP(hipMemsetAsync(d_keep, 0, rows * sizeof(uint8_t), s));
         if (d_owner) PCPX_HIP(hipMemsetAsync(d_owner, 0xFF, rows * sizeof(u32), s));
@@ -222,13 +206,8 @@ int subsample_self(Index& ix, float radius, u32 seed, uint8_t* d_keep, u32* d_ow
         k_subsample_rows<<<blocks_of(n, SS_BLOCK), SS_BLOCK, 0, s>>>(t, state, d_keep);
         PCPX_HIP(hipGetLastError());
     }
-    if (d_kept_rows || d_kept_count) {
-        u32* place = d_kept_rows ? state : nullptr;  // (free by now); place[i] = kept rows among [0, i)
-        if ((st = exclusive_scan(IsKept{d_keep}, rows, sums, place, d_kept_count, s)) != PCPX_OK) return st;
-        if (d_kept_rows) k_subsample_compact<<<blocks_of(rows, SS_BLOCK), SS_BLOCK, 0, s>>>(d_keep, static_cast<u32>(rows), place, d_kept_rows);
-        PCPX_HIP(hipGetLastError());
-    }
-    return PCPX_OK;
+    // (the state words are free by now: the scan's places)
+    return count_and_compact_kept(d_keep, rows, state, sums, d_kept_rows, d_kept_count, s);
 }
 
 }  // namespace pcpx
@@ -252,31 +231,21 @@ int pcpx_subsample_self(pcpx_index* h, float radius, uint32_t seed, uint32_t fla
                         uint32_t* opt_kept_rows, uint64_t* opt_kept_count, uint32_t* opt_rounds)
 {
     static const char* what = "pcpx_subsample_self";
-    return on_index(h, what, WHOLE_CLOUD, [&](Index* ix) -> int {
+    return on_index_host(h, what, WHOLE_CLOUD, [&](Index* ix, Staged& stage) -> int {
         int st;
         if ((st = check_subsample_args(what, radius, flags, keep)) != PCPX_OK) return st;
         if (opt_kept_count) *opt_kept_count = 0;
         if (opt_rounds) *opt_rounds = 0;
         const u64 rows = ix->n_in;
         if (rows == 0) return PCPX_OK;
-        const bool want_count = opt_kept_rows || opt_kept_count;
-        DevBuf dk(ix->pool), dw(ix->pool), dr(ix->pool), dt(ix->pool);
-        if ((st = dk.alloc(rows * sizeof(uint8_t))) != PCPX_OK) return st;
-        if (opt_owner && (st = dw.alloc(rows * sizeof(u32))) != PCPX_OK) return st;
-        if (opt_kept_rows && (st = dr.alloc(rows * sizeof(u32))) != PCPX_OK) return st;
-        if (want_count && (st = dt.alloc(sizeof(u64))) != PCPX_OK) return st;
-        if ((st = subsample_self(*ix, radius, seed, dk.as<uint8_t>(), dw.as<u32>(), dr.as<u32>(), dt.as<u64>(), opt_rounds)) != PCPX_OK) return st;
-        u64 count = 0;
-        PCPX_HIP(hipMemcpyAsync(keep, dk.p, rows * sizeof(uint8_t), hipMemcpyDeviceToHost, ix->stream));
-        if (opt_owner) PCPX_HIP(hipMemcpyAsync(opt_owner, dw.p, rows * sizeof(u32), hipMemcpyDeviceToHost, ix->stream));
-        if (want_count) PCPX_HIP(hipMemcpyAsync(&count, dt.p, sizeof(u64), hipMemcpyDeviceToHost, ix->stream));
-        PCPX_HIP(hipStreamSynchronize(ix->stream));
-        if (opt_kept_count) *opt_kept_count = count;
-        if (opt_kept_rows && count) {  // (count <= rows)
-            PCPX_HIP(hipMemcpyAsync(opt_kept_rows, dr.p, count * sizeof(u32), hipMemcpyDeviceToHost, ix->stream));
-            PCPX_HIP(hipStreamSynchronize(ix->stream));
-        }
-        return PCPX_OK;
+        uint8_t* dk = stage.alloc<uint8_t>(rows * sizeof(uint8_t));
+        u32* dw = stage.alloc_for(opt_owner, rows * sizeof(u32));
+        u32* dr = stage.alloc_for(opt_kept_rows, rows * sizeof(u32));
+        u64* dt = opt_kept_rows || opt_kept_count ? stage.alloc<u64>(sizeof(u64)) : nullptr;
+        if ((st = stage.st) != PCPX_OK || (st = subsample_self(*ix, radius, seed, dk, dw, dr, dt, opt_rounds)) != PCPX_OK) return st;
+        stage.download(keep, dk, rows * sizeof(uint8_t));
+        stage.download_opt(opt_owner, dw, rows * sizeof(u32));
+        return download_kept(stage, dt, dr, opt_kept_count, opt_kept_rows);
     });
 }
 

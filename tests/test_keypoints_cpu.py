@@ -79,9 +79,9 @@ def test_keypoints_null_handle_is_refused(lib):
 def test_keypoints_kernels_use_no_scratch():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), "pcpx_keypoints.hip", "k_"],
                          capture_output=True, text=True, timeout=580, check=True).stdout
-    rows = dict((m[0], [int(v) for v in m[1:]]) for m in re.findall(  # (the scan's kernels are the shared templates of pcpx_scan.h)
-        r"(k_(?:maxima|local_maxima|iss|scan)\w*)(?:<[^\n]*?>)?\(.*?vgpr\s+(\d+) sgpr\s+(\d+) sspill\s+(\d+) vspill\s+(\d+) scratch\s+(\d+) lds\s+(\d+)", out))
-    assert sorted(rows) == sorted(["k_maxima_prep", "k_local_maxima", "k_iss_score", "k_maxima_compact", "k_scan_tile_sums", "k_scan_sums",
+    rows = dict((m[0], [int(v) for v in m[1:]]) for m in re.findall(  # (the scan's kernels are the shared templates of pcpx_scan.h, k_keep_compact is pcpx_keep.h's)
+        r"(k_(?:maxima|local_maxima|iss|keep|scan)\w*)(?:<[^\n]*?>)?\(.*?vgpr\s+(\d+) sgpr\s+(\d+) sspill\s+(\d+) vspill\s+(\d+) scratch\s+(\d+) lds\s+(\d+)", out))
+    assert sorted(rows) == sorted(["k_maxima_prep", "k_local_maxima", "k_iss_score", "k_keep_compact", "k_scan_tile_sums", "k_scan_sums",
                                    "k_scan_tiles"]), out
     assert len(out.strip().splitlines()) == len(rows), out  # (every kernel of the file is among them)
     for name, (_vgpr, _sgpr, sspill, vspill, scratch, lds) in rows.items():

@@ -75,9 +75,9 @@ def test_subsample_null_handle_is_refused(lib):
 def test_subsample_kernels_use_no_scratch():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), "pcpx_subsample.hip", "k_"],
                          capture_output=True, text=True, timeout=580, check=True).stdout
-    rows = dict((m[0], [int(v) for v in m[1:]]) for m in re.findall(  # (the scan's kernels are the shared templates of pcpx_scan.h)
-        r"(k_(?:subsample|scan)_\w+)(?:<[^\n]*?>)?\(.*?vgpr\s+(\d+) sgpr\s+(\d+) sspill\s+(\d+) vspill\s+(\d+) scratch\s+(\d+)", out))
-    assert sorted(rows) == sorted(["k_subsample_init", "k_subsample_round", "k_subsample_owner", "k_subsample_rows", "k_subsample_compact",
+    rows = dict((m[0], [int(v) for v in m[1:]]) for m in re.findall(  # (the scan's kernels are the shared templates of pcpx_scan.h, k_keep_compact is pcpx_keep.h's)
+        r"(k_(?:subsample|keep|scan)_\w+)(?:<[^\n]*?>)?\(.*?vgpr\s+(\d+) sgpr\s+(\d+) sspill\s+(\d+) vspill\s+(\d+) scratch\s+(\d+)", out))
+    assert sorted(rows) == sorted(["k_subsample_init", "k_subsample_round", "k_subsample_owner", "k_subsample_rows", "k_keep_compact",
                                    "k_scan_tile_sums", "k_scan_sums", "k_scan_tiles"]), out
     assert len(out.strip().splitlines()) == len(rows), out  # (every kernel of the file is among them)
     for name, (vgpr, _sgpr, sspill, vspill, scratch) in rows.items():
