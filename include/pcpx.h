@@ -414,11 +414,20 @@ int pcpx_debug_eps_test_mode(pcpx_index* idx, int mode);
  * "long_groups_first" (default 1): a self-kNN launch that repeats the previous one's question on the same tree hands its query
  * groups out by the times that launch recorded, the longest first; "gather_outputs" (default 0: measured slower): input-order
  * normals and counts are written at curve positions and permuted by a gather instead of being scattered from the search kernel;
- * "gather_counts" (default 0: measured slower as well): the same for pcpx_range_count_self_dev's counts. */
+ * "gather_counts" (default 0: measured slower as well): the same for pcpx_range_count_self_dev's counts.
+ * "poison" (a byte, 0 ... 255; anything else is PCPX_ERR_INVALID) is a test switch, not a setting: it waits for the handle's stream,
+ * fills everything that is scratch by contract with that byte -- the handle's scratch block, its k > 32 pass keys, its
+ * per-position gather scratch, its input-index table while that is not valid, its recorded group times and order while nothing is
+ * recorded, the idle blocks of its staging pool; the idle blocks of the device's pool and the leased blocks whose kernels have
+ * finished; the idle index blocks of the device -- and waits again.  No block that is handed out, no tree or cloud array, no
+ * work-queue counter and no flag of the handle is touched.  The content of scratch is unspecified, so every call gives the same bits
+ * after any fill (tests/test_gpu_handle_history.py). */
 int pcpx_debug_set(pcpx_index* idx, const char* name, int64_t value);
 /* Figures of the handle: "build_redos" (builds repeated because the leaf kernel met a run of sort words it could not order),
  * "full_buckets" (top-digit buckets that take every radix pass since), "schedule_state" (0: nothing recorded, 1: group times
- * recorded, 2: the recorded order is in use). */
+ * recorded, 2: the recorded order is in use), "poisoned_bytes" (what the handle's last "poison" filled in all),
+ * "poisoned_shared_bytes" (of that, in the device's pool and its finished leases), "poisoned_cache_bytes" (of that, in the idle
+ * index blocks), "scratch_bytes" (the size of the handle's scratch block now). */
 int pcpx_debug_get(pcpx_index* idx, const char* name, int64_t* out_value);
 /* What the handle's last recorded self-kNN launch took per query group (shader-clock ticks / 64, search only; host array of
  * *out_groups entries, the launch's groups in curve order; 0 groups: nothing recorded).  PCPX_ERR_CAPACITY reports the size. */

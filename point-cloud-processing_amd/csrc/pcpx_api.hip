@@ -1,7 +1,7 @@
 // pcpx_api.hip -- the extern "C" boundary declared in include/pcpx.h (and its companions include/pcpx_radius.h and include/pcpx_features.h).
 // Host-pointer entry points stage through device buffers and are synchronous; *_dev entry points
 // enqueue on the index's stream.  No CPU fallback exists: every compute call needs a HIP device.
-#include "pcpx_stage.h"
+#include "pcpx_lease.h"
 #include "pcpx_radius.h"
 #include "pcpx_features.h"
 
@@ -170,6 +170,49 @@ int knn_self_dev(Index* ix, const char* what, u32 k, float eps, u64 sorted_first
         if (!o.cnt) o.cnt = reinterpret_cast<u32*>(static_cast<char*>(ix->d_scratch) + need_idx);
     }
     return launch_knn(*ix, self_view(*ix), true, gf, gc, k, eps, o);
+}
+
+// pcpx_debug_set "poison": every byte that is scratch by contract -- of the handle, of its device's pool and passed leases, of the
+// idle index blocks -- gets `byte`; nothing that is state (the tree, the cloud, the work-queue counters, a valid d_pos_of, a recorded
+// schedule) and no block that is handed out is touched, and no flag changes.  The handle's stream is drained before and after.
+int poison_scratch(Index& ix, int byte)
+{
+    const hipStream_t s = ix.stream;
+    PCPX_HIP(hipStreamSynchronize(s));
+    u64 own = 0, shared = 0, cache = 0;
+    auto fill = [&](void* p, u64 bytes, u64& sum) -> int {
+        if (!p || !bytes) return PCPX_OK;
+        PCPX_HIP(hipMemsetAsync(p, byte, bytes, s));
+        sum += bytes;
+        return PCPX_OK;
+    };
+    int st;
+    if ((st = fill(ix.d_scratch, ix.scratch_bytes, own)) != PCPX_OK || (st = fill(ix.d_multi, ix.multi_bytes, own)) != PCPX_OK ||
+        (st = fill(ix.d_nc4, ix.nc4_cap, own)) != PCPX_OK)
+        return st;
+    if (!ix.pos_of_valid && (st = fill(ix.d_pos_of, ix.pos_of_cap * sizeof(u32), own)) != PCPX_OK) return st;
+    if (ix.sched.state == 0 && ((st = fill(ix.sched.d_gtime, ix.sched.cap * sizeof(u32), own)) != PCPX_OK ||
+                                (st = fill(ix.sched.d_order, ix.sched.order_entries * sizeof(u32), own)) != PCPX_OK))
+        return st;
+    if ((st = ix.pool.poison(byte, s, &own)) != PCPX_OK) return st;
+    if (ix.device >= 0 && ix.device < LEASE_MAX_DEVICES) {
+        DeviceShared& sh = shared_of(ix.device);
+        std::lock_guard<std::mutex> lock(sh.mu);
+        if ((st = sh.pool.poison(byte, s, &shared)) != PCPX_OK) return st;
+        for (auto const& h : g_held[ix.device]) {
+            if (hipEventQuery(h.passed) != hipSuccess) {  // (hipErrorNotReady: a queued kernel may still read the block)
+                (void)hipGetLastError();
+                continue;
+            }
+            if ((st = fill(h.p, h.bytes, shared)) != PCPX_OK) return st;
+        }
+        PCPX_HIP(hipStreamSynchronize(s));  // (before the device's lock goes: a call on another stream may take these blocks next)
+    }
+    if ((st = index_blocks_poison(byte, s, &cache)) != PCPX_OK) return st;  // (waits for s itself)
+    ix.poisoned_bytes = own + shared + cache;
+    ix.poisoned_shared_bytes = shared;
+    ix.poisoned_cache_bytes = cache;
+    return PCPX_OK;
 }
 
 }  // namespace
@@ -1023,6 +1066,12 @@ int pcpx_debug_set(pcpx_index* h, const char* name, int64_t value)
         ix->tuning.icp_resort = value != 0;
     } else if (key == "icp_previous_start") {
         ix->tuning.icp_previous_start = value < 0 ? -1 : value != 0;
+    } else if (key == "poison") {
+        if (value < 0 || value > 255) {
+            set_error("pcpx_debug_set: poison takes a byte, 0 ... 255");
+            return PCPX_ERR_INVALID;
+        }
+        return poison_scratch(*ix, static_cast<int>(value));
     } else {
         set_error("pcpx_debug_set: no setting called '%s'", name);
         return PCPX_ERR_INVALID;
@@ -1044,6 +1093,14 @@ int pcpx_debug_get(pcpx_index* h, const char* name, int64_t* out_value)
         *out_value = c;
     } else if (key == "schedule_state") {
         *out_value = ix->sched.state;
+    } else if (key == "poisoned_bytes") {
+        *out_value = static_cast<int64_t>(ix->poisoned_bytes);
+    } else if (key == "poisoned_shared_bytes") {
+        *out_value = static_cast<int64_t>(ix->poisoned_shared_bytes);
+    } else if (key == "poisoned_cache_bytes") {
+        *out_value = static_cast<int64_t>(ix->poisoned_cache_bytes);
+    } else if (key == "scratch_bytes") {
+        *out_value = static_cast<int64_t>(ix->scratch_bytes);
     } else {
         set_error("pcpx_debug_get: no figure called '%s'", name);
         return PCPX_ERR_INVALID;

@@ -146,6 +146,7 @@ struct DevPool {
     void* acquire(size_t bytes);  // nullptr (and the thread's error text set) when the device is out of memory
     void release(void* p);
     void trim();                  // frees every block that is not handed out
+    int poison(int byte, hipStream_t s, u64* filled);  // fills every block that is not handed out (pcpx_debug_set "poison")
     size_t cached_bytes() const;
     ~DevPool();
 };
@@ -160,6 +161,7 @@ struct DevPool {
 hipError_t index_block_alloc(void** p, size_t bytes);
 void index_block_free(void* p);
 void index_blocks_trim();  // every idle block of the current device back to the driver
+int index_blocks_poison(int byte, hipStream_t s, u64* filled);  // fills every idle block of the current device on s and waits for s (pcpx_debug_set "poison")
 
 // Streams of handles, kept per device across handles: hipStreamCreate costs 8 ms on this stack and hipStreamDestroy 2 (measured:
 // tools/h2d_probe.hip) -- more than a 2^20-point index build with its upload.  A handle's private streams come from here and go
@@ -237,6 +239,8 @@ struct Index {
     DevPool pool;        // staging buffers of the host-pointer entry points
     PinnedStage pinned;  // small-transfer staging
     u32 few_epoch = 0;   // launch counter of the latency path (its completion flag carries the epoch)
+    u64 poisoned_bytes = 0, poisoned_shared_bytes = 0, poisoned_cache_bytes = 0;  // what the last pcpx_debug_set "poison" filled: in all,
+                                                                                  // of the device's pool and leases, of the idle index blocks
     // ---- long groups first (pcpx_query.hip: k_make_order).  A self-kNN launch records what every group took; when the same question
     // (slice, k class) comes again on the same tree, the launch hands the groups out by those times -- the longest third first, curve
     // order inside a class -- so that a short launch (one rank's eighth of a cloud: 2.7 groups per resident wave) does not end with a
@@ -245,6 +249,7 @@ struct Index {
         u32* d_gtime = nullptr;   // per group of the recorded launch
         u32* d_order = nullptr;
         u64 cap = 0;              // groups both arrays hold
+        u64 order_entries = 0;    // words of d_order
         u64 gf = 0, gc = 0;       // the recorded launch's groups
         int kcap = 0;
         u32 k = 0;

@@ -1572,6 +1572,7 @@ int sched_reserve(Index& ix, u64 groups)
     sc.d_gtime = static_cast<u32*>(a);
     sc.d_order = static_cast<u32*>(b);
     sc.cap = cap;
+    sc.order_entries = order_entries(cap);
     return PCPX_OK;
 }
 

@@ -94,6 +94,15 @@ void DevPool::trim()
     }
     blocks.resize(keep);
 }
+int DevPool::poison(int byte, hipStream_t s, u64* filled)
+{
+    for (auto const& b : blocks)
+        if (!b.used) {
+            PCPX_HIP(hipMemsetAsync(b.p, byte, b.bytes, s));
+            *filled += b.bytes;
+        }
+    return PCPX_OK;
+}
 size_t DevPool::cached_bytes() const
 {
     size_t t = 0;
@@ -208,6 +217,21 @@ void index_blocks_trim()
     IndexBlocks& c = index_blocks();
     std::lock_guard<std::mutex> lock(c.mu);
     free_idle_blocks(c, dev);
+}
+
+int index_blocks_poison(int byte, hipStream_t s, u64* filled)
+{
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    IndexBlocks& c = index_blocks();
+    std::lock_guard<std::mutex> lock(c.mu);
+    for (auto const& b : c.idle)
+        if (b.device == dev) {
+            PCPX_HIP(hipMemsetAsync(b.p, byte, b.bytes, s));
+            *filled += b.bytes;
+        }
+    PCPX_HIP(hipStreamSynchronize(s));  // (before the cache's lock goes: the next index built on the device may take these blocks)
+    return PCPX_OK;
 }
 
 namespace {

@@ -714,11 +714,13 @@ class Index:
         return out
 
     def debug_set(self, name, value):
-        """pcpx_debug_set: 'long_groups_first', 'gather_outputs', 'icp_resort' (how work is done, never what comes out)."""
+        """pcpx_debug_set: 'long_groups_first', 'gather_outputs', 'icp_resort' (how work is done, never what comes out); 'poison' (a byte):
+        fills everything that is scratch by contract, of the handle, its device's pool and the idle index blocks (include/pcpx.h)."""
         check(self._lib.pcpx_debug_set(self._h, name.encode(), int(value)))
 
     def debug_get(self, name):
-        """pcpx_debug_get: 'build_redos', 'full_buckets', 'schedule_state'."""
+        """pcpx_debug_get: 'build_redos', 'full_buckets', 'schedule_state', 'poisoned_bytes', 'poisoned_shared_bytes', 'poisoned_cache_bytes',
+        'scratch_bytes'."""
         v = C.c_int64(0)
         check(self._lib.pcpx_debug_get(self._h, name.encode(), C.byref(v)))
         return int(v.value)
