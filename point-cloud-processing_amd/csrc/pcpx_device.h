@@ -135,6 +135,8 @@ struct WalkerT {
     u64 pend;
     u32 ploc;
     int l;
+    u32 l2;            // 2 * l, carried for pop_scaled() (every member that sets l sets it: a kernel that never reads one of the two does not keep it)
+    u32 lshift0;       // 30 - 2 * depth: level_base(depth - h + 1) = 0x55555555 >> (lshift0 + 2 h), for expand_any()
     u64 leaf_need[W];  // KEEP: valid for the children of the most recently expanded node (the leaves popped next, if it was a last-level node)
 
     // first heap id of tree level d >= 1: (4^d - 1) / 3 = 0b0101...01 (d pairs)
@@ -144,18 +146,25 @@ struct WalkerT {
     template <class Need>
     __device__ __forceinline__ u32 child_mask(const TreeView& t, int d, u32 loc, Need&& need)
     {
-        const u32 first_child = level_base(d + 1) + (loc << LOGW);  // heap id of child 0
+        return child_mask_at(t, level_base(d + 1) + (loc << LOGW), need);
+    }
+    // the same for the node whose child 0 has heap id `first_child`
+    template <class Need>
+    __device__ __forceinline__ u32 child_mask_at(const TreeView& t, u32 first_child, Need&& need)
+    {
         const NodeBox4 cb = X16 ? load_node4(t.nodes + first_child) : load_const(reinterpret_cast<const NodeBox4*>(t.nodes + first_child));
         // the mask is built on the scalar unit, two instructions per child: "some lane needs it" goes to SCC and is shifted
         // into the mask with an add-with-carry (children in reverse order, so child 0 ends up in bit 0).  (Left to itself hipcc
         // makes the mask a vector value: v_cndmask, three v_or and a v_readfirstlane per expansion.)
-        u32 m = 0;
+        // (The first child tested SETS the mask, with a select: no register to clear beforehand.)
+        u32 m;
 #pragma unroll
         for (int c = W - 1; c >= 0; --c) {
             const u64 lanes = __builtin_amdgcn_ballot_w64(need(cb.c[c]));
             if (KEEP) leaf_need[c] = lanes;  // (kept at every expansion, though only a last-level node's are read: keeping them only there
                                              //  measured 2 % SLOWER -- hipcc then moves the masks about at the loop's edges)
-            asm("s_cmp_lg_u64 %1, 0\n\ts_addc_u32 %0, %0, %0" : "+s"(m) : "s"(lanes) : "scc");
+            if (c == W - 1) asm("s_cmp_lg_u64 %1, 0\n\ts_cselect_b32 %0, 1, 0" : "=s"(m) : "s"(lanes) : "scc");
+            else asm("s_cmp_lg_u64 %1, 0\n\ts_addc_u32 %0, %0, %0" : "+s"(m) : "s"(lanes) : "scc");
         }
         return m;
     }
@@ -167,12 +176,16 @@ struct WalkerT {
         pend = 0;
         ploc = 0;
         l = 0;
+        l2 = 0;
+        lshift0 = static_cast<u32>(30 - 2 * t.depth);
+        asm("" : "+s"(lshift0));  // (opaque: hipcc otherwise keeps 2 * depth and adds the 30 on every pop)
         if (t.nleaves == 0) return false;
         const NodeBox root = load_const(t.nodes);
         if (!any_lane(need(root))) return false;
         if (t.depth == 0) return true;
         ++n_expand;
         l = t.depth - 1;
+        l2 = __builtin_amdgcn_readfirstlane(2u * static_cast<u32>(l));  // (or hipcc carries it round k_knn's walk in a vector register)
         pend = static_cast<u64>(child_mask(t, 0, 0u, need)) << (W * l);
         return false;
     }
@@ -194,11 +207,13 @@ struct WalkerT {
     {
         ploc = loc >> LOGW;
         l = 0;
+        l2 = 0;
     }
     template <class Need>
     __device__ __forceinline__ void expand(const TreeView& t, int h, u32 loc, Need&& need)
     {
         l = h - 1;
+        l2 = 2u * static_cast<u32>(l);
         ploc = loc;
         pend |= static_cast<u64>(child_mask(t, t.depth - h, loc, need)) << (W * l);
     }
@@ -210,8 +225,51 @@ struct WalkerT {
     __device__ __forceinline__ u32 leaves_of(const TreeView& t, u32 loc, Need&& need)
     {
         l = 0;
+        l2 = 0;
         ploc = loc;
         return child_mask(t, t.depth - 1, loc, need);
+    }
+
+    // pop() and expand() / leaves_of() for a loop that is short of scalar issue slots (k_knn's walk): ONE expansion for a popped node
+    // of any height h >= 1, and the height handled times W, as it stands in the popped bit's number.
+    //   while (!wk.done()) { u32 loc; u32 h4 = wk.pop_scaled(loc); u32 leaves = wk.expand_any(t, h4, loc, need); ...leaves (loc << LOGW) + c for the set bits c... }
+    // (A loop that calls expand() or leaves_of() by height holds two whole copies of the expansion, and hipcc steers between them
+    //  with a wave-uniform bool kept as a lane mask: seven scalar-class instructions of dispatch, three of them branches, on every pop.
+    //  With h4 = 4 h the climb's shift is (h4 >> 1) - l2, the level's first heap id 0x55555555 >> (30 - 2 depth + (h4 >> 1)) -- the
+    //  first term is the loop's constant -- and the pending bits' shift h4 - 4: four scalar instructions fewer per pop than from h.)
+    __device__ __forceinline__ u32 pop_scaled(u32& loc)
+    {
+        u32 bit;
+        asm("s_ff1_i32_b64 %0, %1\n\ts_bitset0_b64 %1, %0" : "=&s"(bit), "+s"(pend));
+        const u32 h4 = bit & ~(W - 1u);
+        const u32 up = ploc >> ((h4 >> 1) - l2);  // climb h - l levels ...
+        asm("s_lshl2_add_u32 %0, %1, %2" : "=s"(loc) : "s"(up), "s"(bit & (W - 1u)) : "scc");  // ... step down (hipcc: shift, and, or)
+        static_assert(LOGW == 2, "s_lshl2_add_u32");
+        return h4;
+    }
+    // One child_mask at level depth - h.  The mask of a node above the last level goes to the pending bits, a last-level node's is
+    // returned (its needed leaves, as from leaves_of; 0 for a higher node).  ONE scalar branch on the height does that (s_cmp_eq_u32,
+    // s_cbranch_scc1): routed by two s_cselect_b32 instead, a last-level node -- more than a third of the pops -- pays for the push it
+    // does not need, and the loop was no faster than with the two copies (profiles/experiments/README.md).  The push is an asm
+    // statement, or hipcc turns the branch back into selects on a lane mask.
+    template <class Need>
+    __device__ __forceinline__ u32 expand_any(const TreeView& t, u32 h4, u32 loc, Need&& need)
+    {
+        const u32 h2 = h4 >> 1;
+        const u32 base = 0x55555555u >> (lshift0 + h2);  // level_base(depth - h + 1)
+        u32 first_child;
+        asm("s_lshl2_add_u32 %0, %1, %2" : "=s"(first_child) : "s"(loc), "s"(base) : "scc");
+        const u32 m = child_mask_at(t, first_child, need);
+        l = static_cast<int>(h4 >> LOGW) - 1;
+        l2 = h2 - 2u;
+        ploc = loc;
+        u32 direct = m;
+        if (h4 != W) {  // above the last level
+            u64 pushed;
+            asm("s_lshl_b64 %[t], %[m], %[sh]\n\ts_or_b64 %[p], %[p], %[t]" : [p] "+s"(pend), [t] "=&s"(pushed) : [m] "s"(static_cast<u64>(m)), [sh] "s"(h4 - W) : "scc");
+            direct = 0;
+        }
+        return direct;
     }
 
     template <class Need>
@@ -225,11 +283,13 @@ struct WalkerT {
             if (h == 0) {
                 ploc = loc >> LOGW;
                 l = 0;
+                l2 = 0;
                 leaf = loc;
                 return true;
             }
             ++n_expand;
             l = h - 1;
+            l2 = 2u * static_cast<u32>(l);
             ploc = loc;
             pend |= static_cast<u64>(child_mask(t, t.depth - h, loc, need)) << (W * l);
         }

@@ -613,6 +613,7 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
     for (int j = 0; j < KCAP; ++j) best[j] = (j < KCAP - static_cast<int>(k)) ? 0ull : PAD_KEY;
     const float inf = std::numeric_limits<float>::infinity();
     float tau = valid ? inf : -1.f;  // -1: an idle lane never accepts a candidate nor needs a node
+    float tau_slack = box_bound_tau(tau);  // what the node tests compare with, formed where tau changes (a fold), not at every expansion
     // diagnostic build only: o.d2 holds the FINAL rows of an earlier run; starting from the true k-th distance
     // measures how much of the walk is spent before tau has tightened (the floor any visiting order can reach)
     float tau_known = inf;
@@ -629,8 +630,8 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
     constexpr int packed_free = KCAP <= 16 ? PACKED_FREE16 : 0;  // (see PACKED_FREE16)
     const u32 wa_packed_full = packed_free > 0 ? lds_row0 + (static_cast<u32>(BUF - packed_free + 1) << 9) : wa_full;
 
-    // (node tests only: the fused bound against the slackened tau, pcpx_box_bound.h; hipcc forms the slackened tau once per expansion)
-    auto need = [&](const NodeBox& b) { return box_bound_fused(b, qx, qy, qz) <= box_bound_tau(tau); };
+    // (node tests only: the fused bound against the slackened tau, pcpx_box_bound.h; the slackened tau is kept beside tau: tau_slack)
+    auto need = [&](const NodeBox& b) { return box_bound_fused(b, qx, qy, qz) <= tau_slack; };
     // single-pass kernels: the eps-box test waits for the compaction, unless the launcher picked the EPS_EACH form (launch_knn_t)
     const EpsFilter eps_filter{deferred_eps(MULTI, EPS_EACH), eps_thr, eps, qx, qy, qz, t.leaves};
 
@@ -680,6 +681,7 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
         float nt = __uint_as_float(static_cast<u32>(best[KCAP - 1] >> 32));
         tau = active ? fminf(nt, cap) : -1.f;
         if (STATS) tau = fminf(tau, tau_known);
+        tau_slack = box_bound_tau(tau);
         wa = col_addr + (static_cast<u32>(cnt) << 9);
         if (COST) ++st_compact;
         if (STATS) {
@@ -799,6 +801,7 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
         for (int j = 0; j < LEAF; ++j) best[KCAP - 1 - j] = key_min(best[KCAP - 1 - j], nw[j]);
         bitonic_merge<KCAP, NZ, LEAF>(best);
         tau = active ? fminf(__uint_as_float(static_cast<u32>(best[KCAP - 1] >> 32)), cap) : -1.f;
+        tau_slack = box_bound_tau(tau);
     };
     // (the seed leaves from the middle of the range outwards instead of in curve order -- the middle of the group's own chunk is near
     //  most of its lanes -- was measured in round 4: no gain; profiles/experiments/README.md)
@@ -815,6 +818,7 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
     if (STATS) st_seed_app = st_app;
     cap = wave_radius_cap<KCAP>(tau, valid, lane);
     tau = active ? fminf(tau, cap) : -1.f;
+    tau_slack = box_bound_tau(tau);
 
     // ---- walk rounds ----
     constexpr bool packed_leaves = pack_rows(MULTI, KCAP) > 0 && fast && !EPS_EACH;  // (wants the lanes that need each leaf: WalkerT's KEEP)
@@ -929,58 +933,46 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
         const u32 packed_limit_now = __builtin_amdgcn_readfirstlane(packed_limit);
         bool root_leaf = wk.start(t, need, st_expand);
         (void)root_leaf;  // depth 0: the only leaf is the seed chunk, already done
-        // A trip of the outer loop pops one node: a node above the last level is expanded; a LAST-LEVEL node hands its needed
-        // leaves to the inner loop directly (WalkerT::leaves_of: no trip through the pending bits for them -- a dozen scalar
+        // A trip of the outer loop pops one node and expands it (WalkerT::expand_any: one copy of the expansion for every height); a
+        // LAST-LEVEL node hands its needed leaves to the inner loop directly (no trip through the pending bits for them -- a dozen scalar
         // instructions per leaf, and the scalar side of this kernel is what it is short of); `direct` = its children still to look
-        // at, as leaves direct_first + c.  A leaf inside the seed range was seen under a larger tau than any later one: skipped.
+        // at, as leaves (direct_node << LOGW) + c.  A leaf inside the seed range was seen under a larger tau than any later one: skipped.
         if (STATS) tc_mark = __builtin_amdgcn_s_memtime();
-        u32 direct = 0, direct_first = 0;
+        u32 direct = 0, direct_node = 0;
         for (;;) {
             if (direct == 0) {
                 if (wk.done()) break;
-                u32 node;
-                const int h = wk.pop(node);
+                const u32 h4 = wk.pop_scaled(direct_node);
                 ++st_expand;
-                if (h > 1) {
-                    wk.expand(t, h, node, need);
-                } else {
-                    direct_first = node << LOGW;
-                    direct = wk.leaves_of(t, node, need);
-                }
+                direct = wk.expand_any(t, h4, direct_node, need);  // (one expansion for every height: 0 unless the node is a last-level one)
                 // (h = 0 is never popped: the build gives no tree a depth of 1 -- depth_of, pcpx_build.hip -- so leaves are only ever met under a
                 //  last-level node.  The case for it cost EVERY pop of the walk nine scalar instructions of dispatch.)
             }
             while (direct != 0) {
-                u32 loc;
-                {
-                    u32 child;
-                    asm("s_ff1_i32_b32 %0, %1\n\ts_bitset0_b32 %1, %0" : "=&s"(child), "+s"(direct));
-                    loc = direct_first + child;
-                }
+                u32 loc, child;
+                asm("s_ff1_i32_b32 %0, %1\n\ts_bitset0_b32 %1, %0\n\ts_lshl2_add_u32 %2, %3, %0" : "=&s"(child), "+s"(direct), "=s"(loc) : "s"(direct_node) : "scc");
                 if (loc - s0 >= seed_count) {
                     if (STATS) tc_walk += __builtin_amdgcn_s_memtime() - tc_mark;
                     if (!packed_leaves) {
                         fold_if_needed(true, false);
                         candidates(loc, rounds != 0u);
                     } else {
-                        const u32 c = loc & (W - 1u);
-                        u64 who;
-                        u32 how_many;
-                        asm("s_cmp_eq_u32 %[c], 2\n\ts_cselect_b64 %[w], %[n2], %[n3]\n\t"
-                            "s_cmp_eq_u32 %[c], 1\n\ts_cselect_b64 %[w], %[n1], %[w]\n\t"
-                            "s_cmp_eq_u32 %[c], 0\n\ts_cselect_b64 %[w], %[n0], %[w]\n\t"
-                            "s_bcnt1_i32_b64 %[m], %[w]"
-                            : [w] "=&s"(who), [m] "=s"(how_many)
-                            : [c] "s"(c), [n0] "s"(wk.leaf_need[0]), [n1] "s"(wk.leaf_need[1]), [n2] "s"(wk.leaf_need[2]), [n3] "s"(wk.leaf_need[3])
-                            : "scc");
+                        const u32 c = child;
+                        // The lanes that need the leaf: leaf_need[c], picked bit by bit of c (two tests, three selects), and their number.
                         // Only a lane that needs the leaf can take keys from it (its box distance was within a tau that has only
                         // shrunk since, and no point of the leaf is nearer than its box): fold if one of THOSE could not take LEAF more.
                         // (The form is a NUMBER in a scalar register and "once more, after a fold" a threshold of 0: as two bools carried round
-                        //  the loop hipcc kept them as 64-bit lane masks -- a dozen scalar instructions per leaf to set, copy and test them.)
-                        u32 packed_form, full_from;
-                        asm("s_cmp_le_u32 %[m], %[lim]\n\ts_cselect_b32 %[pf], 1, 0\n\ts_cselect_b32 %[thr], %[tp], %[td]"
-                            : [pf] "=&s"(packed_form), [thr] "=&s"(full_from)
-                            : [m] "s"(how_many), [lim] "s"(packed_limit_now), [tp] "s"(wa_packed_full), [td] "s"(wa_full)
+                        //  the loop hipcc kept them as 64-bit lane masks -- a dozen scalar instructions per leaf to set, copy and test them.
+                        //  One statement: between two asm statements in a row hipcc puts an s_nop.)
+                        u64 who, upper;
+                        u32 how_many, packed_form, full_from;
+                        asm("s_bitcmp1_b32 %[c], 0\n\ts_cselect_b64 %[w], %[n1], %[n0]\n\ts_cselect_b64 %[u], %[n3], %[n2]\n\t"
+                            "s_bitcmp1_b32 %[c], 1\n\ts_cselect_b64 %[w], %[u], %[w]\n\t"
+                            "s_bcnt1_i32_b64 %[m], %[w]\n\t"
+                            "s_cmp_le_u32 %[m], %[lim]\n\ts_cselect_b32 %[pf], 1, 0\n\ts_cselect_b32 %[thr], %[tp], %[td]"
+                            : [w] "=&s"(who), [u] "=&s"(upper), [m] "=&s"(how_many), [pf] "=&s"(packed_form), [thr] "=&s"(full_from)
+                            : [c] "s"(c), [n0] "s"(wk.leaf_need[0]), [n1] "s"(wk.leaf_need[1]), [n2] "s"(wk.leaf_need[2]), [n3] "s"(wk.leaf_need[3]),
+                              [lim] "s"(packed_limit_now), [tp] "s"(wa_packed_full), [td] "s"(wa_full)
                             : "scc");
                         u64 todo = who;  // (the lanes the leaf is still to be looked at for)
                         for (;;) {  // (one call site of the fold: one copy of the selection network)
@@ -1041,6 +1033,7 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
         cap = (grown > cap && grown < diag2 * 4.f && rounds < 12u) ? grown : inf;
         active = failed;
         tau = active ? fminf(kth, cap) : -1.f;
+        tau_slack = box_bound_tau(tau);
         cnt = 0;
         wa = col_addr;
     }
