@@ -384,7 +384,7 @@ int pcpx_bounding_box_dev(const float* d_xyz, uint64_t n, int device, void* stre
     DevBuf enc(shared.pool);
     if ((st = enc.alloc(64 * sizeof(u32))) != PCPX_OK) return st;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    st = device_bbox(d_xyz, n, s, enc.as<u32>(), d_out6);
+    st = device_bbox(d_xyz, n, s, enc.as<u32>(), d_out6, false);
     if (st != PCPX_OK) return st;
     PCPX_HIP(hipStreamSynchronize(s));  // enc goes back to the pool on return
     return PCPX_OK;
@@ -400,7 +400,7 @@ int pcpx_bounding_box(const float* xyz, uint64_t n, int device, float out6[6])
     if ((st = box.alloc(64 * sizeof(u32))) != PCPX_OK) return st;
     if (n > 0) PCPX_HIP(hipMemcpy(pts.p, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice));
     float* d_out = box.as<float>() + 32;
-    if ((st = device_bbox(pts.as<float>(), n, nullptr, box.as<u32>(), d_out)) != PCPX_OK) return st;
+    if ((st = device_bbox(pts.as<float>(), n, nullptr, box.as<u32>(), d_out, false)) != PCPX_OK) return st;
     PCPX_HIP(hipMemcpy(out6, d_out, 6 * sizeof(float), hipMemcpyDeviceToHost));
     return PCPX_OK;
     });

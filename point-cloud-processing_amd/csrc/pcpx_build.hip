@@ -33,7 +33,10 @@ __device__ __forceinline__ float dec_f(u32 e)
 }
 
 // pcp::bounding_box (include/pcp/common/axis_aligned_bounding_box.hpp:214-251): min/max per axis
-// from +-FLT_MAX with strict comparisons (NaN coordinates never update).
+// from +-FLT_MAX with strict comparisons (NaN coordinates never update, +-inf ones do).  That is pcpx_bounding_box.  The box an
+// index makes its grid from (FINITE_ONLY) is the box of the points that have three finite coordinates: a point with a NaN or an
+// infinite one is never indexed ("Non-finite coordinates") -- one row at +inf would otherwise stretch the
+// grid until every other point falls into curve cell 0.
 __global__ void k_bbox_init(u32* enc6, u32* counter)
 {
     if (threadIdx.x < 3) enc6[threadIdx.x] = enc_f(std::numeric_limits<float>::max());
@@ -46,8 +49,16 @@ __global__ void k_bbox_init(u32* enc6, u32* counter)
 // t, t + stride, ... and every load instruction of a wave covers a contiguous run of memory (three interleaved 48-byte
 // strides).  Block-level reduction in LDS, then ONE set of six atomics per block (round 1: stride-3 scalar loads and six
 // atomics per wave -- 576 us for 10 M points, 2.6 % of the HBM rate).
+template <bool FINITE_ONLY>
 __device__ __forceinline__ void bbox_point(float (&mn)[3], float (&mx)[3], float x, float y, float z)
 {
+    if (FINITE_ONLY) {  // such a point counts as three NaN: the strict comparisons below never take one (selects, no branch)
+        const float inf = std::numeric_limits<float>::infinity(), nan = __builtin_nanf("");
+        const bool finite = (fabsf(x) < inf) & (fabsf(y) < inf) & (fabsf(z) < inf);  // (false for NaN)
+        x = finite ? x : nan;
+        y = finite ? y : nan;
+        z = finite ? z : nan;
+    }
     if (x < mn[0]) mn[0] = x;
     if (y < mn[1]) mn[1] = y;
     if (z < mn[2]) mn[2] = z;
@@ -56,6 +67,7 @@ __device__ __forceinline__ void bbox_point(float (&mn)[3], float (&mx)[3], float
     if (z > mx[2]) mx[2] = z;
 }
 
+template <bool FINITE_ONLY>
 __global__ __launch_bounds__(256) void k_bbox(const float* __restrict__ xyz, u64 n, u32* enc6)
 {
     float mn[3] = {std::numeric_limits<float>::max(), std::numeric_limits<float>::max(),
@@ -75,21 +87,21 @@ __global__ __launch_bounds__(256) void k_bbox(const float* __restrict__ xyz, u64
         const u64 q2 = q + gstride < nquad ? q + gstride : q;  // (the last trip may repeat its quad: min/max do not mind)
         const float4 a = v[3 * q], b = v[3 * q + 1], c = v[3 * q + 2];
         const float4 d = v[3 * q2], e = v[3 * q2 + 1], f = v[3 * q2 + 2];
-        bbox_point(mn, mx, a.x, a.y, a.z);
-        bbox_point(mn, mx, a.w, b.x, b.y);
-        bbox_point(mn, mx, b.z, b.w, c.x);
-        bbox_point(mn, mx, c.y, c.z, c.w);
-        bbox_point(mn, mx, d.x, d.y, d.z);
-        bbox_point(mn, mx, d.w, e.x, e.y);
-        bbox_point(mn, mx, e.z, e.w, f.x);
-        bbox_point(mn, mx, f.y, f.z, f.w);
+        bbox_point<FINITE_ONLY>(mn, mx, a.x, a.y, a.z);
+        bbox_point<FINITE_ONLY>(mn, mx, a.w, b.x, b.y);
+        bbox_point<FINITE_ONLY>(mn, mx, b.z, b.w, c.x);
+        bbox_point<FINITE_ONLY>(mn, mx, c.y, c.z, c.w);
+        bbox_point<FINITE_ONLY>(mn, mx, d.x, d.y, d.z);
+        bbox_point<FINITE_ONLY>(mn, mx, d.w, e.x, e.y);
+        bbox_point<FINITE_ONLY>(mn, mx, e.z, e.w, f.x);
+        bbox_point<FINITE_ONLY>(mn, mx, f.y, f.z, f.w);
     }
     // the peeled points and the tail (fewer than 8 in all): the first threads of the grid take one each
     const u64 tail0 = head + 4 * nquad;
     const u64 loose = head + (n - tail0);
     if (gtid < loose) {
         const u64 i = gtid < head ? gtid : tail0 + (gtid - head);
-        bbox_point(mn, mx, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
+        bbox_point<FINITE_ONLY>(mn, mx, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
     }
     __shared__ float red[4][6];
 #pragma unroll
@@ -613,19 +625,21 @@ int dev_alloc(T*& p, size_t count, DevPool* pool)
 
 }  // namespace
 
-static void launch_bbox(const float* d_xyz, u64 n, hipStream_t s, u32* d_enc6)
+static void launch_bbox(const float* d_xyz, u64 n, hipStream_t s, u32* d_enc6, bool finite_only)
 {
     u64 blocks = (n / 4 + 255) / 256;  // a thread takes four points per trip
     if (blocks > 1024) blocks = 1024;   // (every block ends with six atomics on the same six words: 2048 blocks spent a third of the
                                         //  10 M-point launch there)
     if (blocks < 1) blocks = 1;
-    k_bbox<<<static_cast<unsigned>(blocks), 256, 0, s>>>(d_xyz, n, d_enc6);
+    if (finite_only) k_bbox<true><<<static_cast<unsigned>(blocks), 256, 0, s>>>(d_xyz, n, d_enc6);
+    else k_bbox<false><<<static_cast<unsigned>(blocks), 256, 0, s>>>(d_xyz, n, d_enc6);
 }
 
-int device_bbox(const float* d_xyz, u64 n, hipStream_t s, u32* d_enc6, float* d_out6)
+// finite_only: the box of the finite points, for a grid (see bbox_point); else pcp::bounding_box's
+int device_bbox(const float* d_xyz, u64 n, hipStream_t s, u32* d_enc6, float* d_out6, bool finite_only)
 {
     k_bbox_init<<<1, 64, 0, s>>>(d_enc6, d_enc6 + 6);
-    if (n > 0) launch_bbox(d_xyz, n, s, d_enc6);
+    if (n > 0) launch_bbox(d_xyz, n, s, d_enc6, finite_only);
     k_bbox_decode<<<1, 64, 0, s>>>(d_enc6, d_out6);
     return check_hip(hipGetLastError(), "bbox kernels", __FILE__, __LINE__);
 }
@@ -767,7 +781,7 @@ int build_box_and_codes(Index& ix, const float* d_xyz_src, u64 n, const pcpx_bui
         PCPX_HIP(hipMemcpyAsync(d_box, g, sizeof(g), hipMemcpyHostToDevice, s));
         PCPX_HIP(hipStreamSynchronize(s));  // g is a stack temporary
     } else if (n > 0) {
-        launch_bbox(d_xyz_src, n, s, ix.d_scalars);
+        launch_bbox(d_xyz_src, n, s, ix.d_scalars, true);
     }
     u64 blocks = (n + SORT_TILE_WORDS - 1) / SORT_TILE_WORDS;  // a block takes whole tiles
     if (blocks > 512) blocks = 512;  // two resident blocks per CU
@@ -830,11 +844,16 @@ int build_index(Index& ix, const float* d_xyz_src, u64 n, const pcpx_build_param
     }
     bool use_grid = params && (params->flags & PCPX_BUILD_USE_GRID);
     if (use_grid) {
-        for (int a = 0; a < 3; ++a)
-            if (!(params->grid_min[a] <= params->grid_max[a])) {
+        for (int a = 0; a < 3; ++a) {
+            if (!(params->grid_min[a] <= params->grid_max[a])) {  // (false for a NaN bound)
                 set_error("pcpx: voxel grid min must not exceed max on every axis");
                 return PCPX_ERR_INVALID;
             }
+            if (!std::isfinite(params->grid_min[a]) || !std::isfinite(params->grid_max[a])) {  // (an infinite extent has no cells)
+                set_error("pcpx: voxel grid bounds must be finite");
+                return PCPX_ERR_INVALID;
+            }
+        }
     }
     if (params && (params->flags & PCPX_BUILD_SHARD)) return build_shard_index(ix, d_xyz_src, n, params);
     hipStream_t s = ix.stream;

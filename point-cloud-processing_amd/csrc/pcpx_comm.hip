@@ -190,7 +190,7 @@ int pcpx_comm_global_grid_dev(pcpx_comm* h, const float* d_xyz_slice, uint64_t n
     float* d_all = cm->d_work + 16;
     float* d_union = d_all + 6 * cm->world;
     // an empty slice contributes the empty box {+FLT_MAX.., -FLT_MAX..}: the identity of the union (axis_aligned_bounding_box.hpp:214-251)
-    int st = device_bbox(d_xyz_slice, n_slice, s, reinterpret_cast<u32*>(cm->d_work), d_local);
+    int st = device_bbox(d_xyz_slice, n_slice, s, reinterpret_cast<u32*>(cm->d_work), d_local, true);  // (a grid: the finite points)
     if (st != PCPX_OK) return st;
     if ((st = check_nccl(rccl().AllGather(d_local, d_all, 6, ncclFloat32, cm->comm, s), "ncclAllGather")) != PCPX_OK) return st;
     k_union_boxes<<<1, 64, 0, s>>>(d_all, cm->world, d_union);

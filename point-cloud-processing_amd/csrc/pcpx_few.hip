@@ -126,7 +126,20 @@ __global__ __launch_bounds__(64) void k_knn_few(TreeView t, const float* __restr
     u32* row_idx = out_idx + static_cast<u64>(qi) * k;
     float* row_d2 = out_d2 ? out_d2 + static_cast<u64>(qi) * k : nullptr;
     if (lane == 0) flags[qi] = 0u;
-    if (t.nleaves == 0) {
+    // Non-finite queries: a NaN coordinate makes every d2 NaN, which is never <= tau -- an empty row, written
+    // here as for an empty index (the sweep below would keep every node: fmaxf drops the NaN axis of a box distance).  An infinite
+    // one puts every point at d2 = +inf, an ordinary value: the row is k points tied at +inf (which of them is unspecified), but the
+    // beam keeps only boxes at a finite distance -- such a query is flagged for the general path, whose walk takes the tie as it comes.
+    const bool q_nan = !(qx == qx && qy == qy && qz == qz);
+    if (!q_nan && (fabsf(qx) == inf || fabsf(qy) == inf || fabsf(qz) == inf) && t.nleaves != 0) {
+        if (lane == 0) {
+            out_cnt[qi] = 0u;
+            flags[qi] = 1u;
+        }
+        signal_done();
+        return;
+    }
+    if (t.nleaves == 0 || q_nan) {
         if (lane < k) {
             row_idx[lane] = INVALID_ID;
             if (row_d2) row_d2[lane] = inf;

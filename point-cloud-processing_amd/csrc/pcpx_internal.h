@@ -366,7 +366,7 @@ int shard_knn_self(Index& ix, u64 sorted_first, u64 sorted_count, u32 k, float e
 int shard_range_count_self(Index& ix, float radius, u64 sorted_first, u64 sorted_count, u32* d_out_cnt, bool by_position = false);
 int shard_unsupported(const Index& ix, const char* what);
 int shard_perm(Index& ix, u32* d_out_perm, u32* d_out_pos);
-int device_bbox(const float* d_xyz, u64 n, hipStream_t s, u32* d_enc6, float* d_out6);
+int device_bbox(const float* d_xyz, u64 n, hipStream_t s, u32* d_enc6, float* d_out6, bool finite_only);  // finite_only: the box a grid is made from
 // stable radix sort of 64-bit words by their bits [first_bit, 64) (first_bit a multiple of 8); words that agree on
 // those bits keep their input order.  sort_failure_flag: device word of the temporary storage that the sort sets if its
 // look-back ever gave up (it never should); read it after synchronising the stream.

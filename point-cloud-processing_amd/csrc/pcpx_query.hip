@@ -598,6 +598,19 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
             qz = cold(&ka->qv.qz)[p];
         }
     }
+    // A query with a NaN coordinate has no neighbour: every d2 is NaN, and NaN <= tau is false.  The search
+    // cannot carry it -- the selection network orders keys as doubles, where a NaN's bits are a negative number (sign set), a NaN, or
+    // a value beyond PAD_KEY, and the node tests' fmaxf drops the NaN axis, so the lane would want every node.  Its lane sits the
+    // search out as an idle one does, on a finite query, and the epilogue gives it an empty row (nan_query_row).  An indexed point
+    // is finite, so self queries have no such lane.
+    bool searching = valid;
+    if (!SELF) {
+        const bool q_nan = !(qx == qx && qy == qy && qz == qz);
+        searching = valid && !q_nan;
+        qx = q_nan ? 0.f : qx;
+        qy = q_nan ? 0.f : qy;
+        qz = q_nan ? 0.f : qz;
+    }
     // (the query's coordinates are waited for here, once: left pending, hipcc puts three s_waitcnt vmcnt in front of their first
     //  use in every block of the search loop -- six scalar-pipe instructions per leaf + expansion)
     asm volatile("" : "+v"(qx), "+v"(qy), "+v"(qz));
@@ -612,13 +625,13 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
 #pragma unroll
     for (int j = 0; j < KCAP; ++j) best[j] = (j < KCAP - static_cast<int>(k)) ? 0ull : PAD_KEY;
     const float inf = std::numeric_limits<float>::infinity();
-    float tau = valid ? inf : -1.f;  // -1: an idle lane never accepts a candidate nor needs a node
+    float tau = searching ? inf : -1.f;  // -1: an idle lane never accepts a candidate nor needs a node
     float tau_slack = box_bound_tau(tau);  // what the node tests compare with, formed where tau changes (a fold), not at every expansion
     // diagnostic build only: o.d2 holds the FINAL rows of an earlier run; starting from the true k-th distance
     // measures how much of the walk is spent before tau has tightened (the floor any visiting order can reach)
     float tau_known = inf;
     if (STATS && known_d2 && valid && SELF) tau_known = known_d2[static_cast<u64>(t.leaves[p / LEAF].id[p % LEAF]) * k + (k - 1)];
-    bool active = valid;             // lanes still searching (the second walk round keeps only the failed ones)
+    bool active = searching;         // lanes still searching (the second walk round keeps only the failed ones)
     int cnt = 0;
     const u32 col_addr = lds_address(col);  // byte address of row 0 of this lane's column
     u32 wa = col_addr;                      // byte address of the next free row (exec-masked accept)
@@ -816,7 +829,7 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
         candidates(leaf, false);
     }
     if (STATS) st_seed_app = st_app;
-    cap = wave_radius_cap<KCAP>(tau, valid, lane);
+    cap = wave_radius_cap<KCAP>(tau, SELF ? valid : active, lane);  // (batch: the lanes that search -- no round has ended yet, `active` is still that)
     tau = active ? fminf(tau, cap) : -1.f;
     tau_slack = box_bound_tau(tau);
 
@@ -1088,6 +1101,30 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
         }
     }
     const int first_slot = KCAP - static_cast<int>(k);
+    // nan_query_row: the lane of a query with a NaN coordinate sat the search out on a finite stand-in (lane setup); whatever its seed
+    // leaves merged into its list is no neighbour.  The query is read again rather than a flag kept through the search, and every
+    // slot from NZ on becomes PAD_KEY (the sentinels among them are read by nothing below but the order check, where equal keys
+    // are in order) by bit arithmetic on an opaque all-ones / zero word: as `nan && s >= first_slot ? PAD_KEY : best[s]` every slot
+    // gets a lane mask or a scalar select of its own, and KCAP of them at once spill.
+    if (!SELF) {
+        const knn_args_ptr kq = knn_args_here();
+        u32 pq = g * GROUP + lane;
+        asm volatile("" : "+v"(pq));
+        float x = 0.f, y = 0.f, z = 0.f;
+        if (valid) {
+            x = cold(&kq->qv.qx)[pq];
+            y = cold(&kq->qv.qy)[pq];
+            z = cold(&kq->qv.qz)[pq];
+        }
+        u32 kill = (x == x && y == y && z == z) ? 0u : ~0u;
+        asm volatile("" : "+v"(kill));
+#pragma unroll
+        for (int s = NZ; s < KCAP; ++s) {
+            const u32 lo = static_cast<u32>(best[s]) | kill;
+            const u32 hi = (static_cast<u32>(best[s] >> 32) & ~kill) | (static_cast<u32>(PAD_KEY >> 32) & kill);
+            best[s] = (static_cast<u64>(hi) << 32) | lo;
+        }
+    }
     // (the cold arguments are read again where the epilogue needs them: nothing read through `ka` above is alive any more)
     if (MULTI) {  // raw (d2, sorted position) keys of this pass; rows are built by k_assemble
         const MultiPass mp = cold(&knn_args_here()->mp);

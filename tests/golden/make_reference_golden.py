@@ -19,6 +19,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import far_cloud_cases as FC  # noqa: E402
+import nonfinite_cases as NF  # noqa: E402
 import surface_nets_model as M  # noqa: E402
 from oracle import pcp_ref as R  # noqa: E402
 
@@ -218,10 +219,41 @@ def far():
     return _save("ref_far.npz", **out)
 
 
+NONFINITE_CLOUDS = ("nan_rows", "odd_nans")  # (a cloud with an infinite coordinate stops the reference on an assertion: not recorded)
+NONFINITE_QUERIES = 200
+
+
+def nonfinite():
+    """The clouds and fields of tests/nonfinite_cases.py are rebuilt by the test (only their SHA-256 is stored).  Clouds of 1 300 points
+    with NaN coordinates in 40 rows: the octree's size, kNN rows at k = 15 for the first 200 points of the finite base cloud, the
+    counts of the case's spheres (radii NaN, -1, 0, +inf among them), the lists of those with a finite radius, and the lists of its
+    boxes.  Distance fields with NaN, +inf and -inf corners: the whole-grid mesh."""
+    out = {}
+    q = np.ascontiguousarray(NF.base(1300)[:NONFINITE_QUERIES])
+    centres, radii = NF.spheres()
+    ok = np.isfinite(centres).all(1)  # (the reference is asked what it defines: finite centres; any radius)
+    listed = ok & np.isfinite(radii)
+    out["sphere_rows"], out["sphere_listed"] = np.nonzero(ok)[0].astype(np.uint32), np.nonzero(listed)[0].astype(np.uint32)
+    for kind in NONFINITE_CLOUDS:
+        pts, _finite = NF.cloud(kind, 1300)
+        t = R.Octree(pts)
+        out[kind + "_sha"] = _sha(pts)
+        out[kind + "_size"] = np.uint64(t.size())
+        out[kind + "_idx"], out[kind + "_cnt"] = t.knn(q, 15, 1e-5)
+        out[kind + "_sphere_cnt"] = np.array([len(t.range_sphere(c, r)) for c, r in zip(centres[ok], radii[ok])], np.uint32)
+        out[kind + "_sphere_off"], out[kind + "_sphere_idx"] = _csr([np.sort(t.range_sphere(c, r)) for c, r in zip(centres[listed], radii[listed])])
+        out[kind + "_box_off"], out[kind + "_box_idx"] = _csr([np.sort(t.range_aabb(b[:3], b[3:])) for b in NF.boxes()])
+    for name in NF.FIELDS:
+        g, f = NF.field(name)
+        out[name + "_sha"] = _sha(f)
+        out[name + "_v"], out[name + "_t"] = R.surface_nets(f, g, 0.0)
+    return _save("ref_nonfinite.npz", **out)
+
+
 def main():
     if not R.available():
         sys.exit("no build of the reference: %s" % R.why_unavailable())
-    total = knn() + ranges() + kd() + surface() + wlop() + far()
+    total = knn() + ranges() + kd() + surface() + wlop() + far() + nonfinite()
     print("%-24s %7d bytes" % ("total", total))
     assert total <= 1536 * 1024
 
