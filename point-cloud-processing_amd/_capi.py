@@ -53,6 +53,11 @@ class PlaneParams(C.Structure):
                 ("min_inliers", C.c_uint32), ("max_planes", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class VoxelParams(C.Structure):
+    """pcpx_voxel_params (include/pcpx_voxel.h)."""
+    _fields_ = [("leaf", C.c_float * 3), ("origin", C.c_float * 3), ("flags", C.c_uint32), ("attr_columns", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 K_BUILD, K_KNN, K_NORMALS, K_RANGE, K_QUERY_PREP = range(5)
 
 
@@ -333,6 +338,19 @@ PLANES_SIGNATURES = {
                                       C.c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/pcpx_voxel.h (voxel-grid downsampling)
+PCPX_VOXEL_ORIGIN = 1
+PCPX_VOXEL_NONE = 0xFFFFFFFF
+PCPX_VOXEL_ATTRS_MAX = 16
+_pvp = C.POINTER(VoxelParams)
+VOXEL_SIGNATURES = {
+    "pcpx_voxel_plan": (C.c_int, [C.c_uint64, C.c_uint64, u64p, u64p]),
+    "pcpx_voxel_grid_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, _pvp, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcpx_voxel_grid": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, _pvp, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 
 def load():
     """Load libpcpx.so; raises if it has not been built (run __graft_entry__.build())."""
@@ -348,7 +366,8 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(RADIUS_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items())\
             + list(SUBSAMPLE_SIGNATURES.items()) + list(SEGMENT_SIGNATURES.items()) + list(FEATURES_SIGNATURES.items())\
             + list(KEYPOINTS_SIGNATURES.items()) + list(DESCRIPTORS_SIGNATURES.items()) + list(MATCH_SIGNATURES.items())\
-            + list(REGISTER_SIGNATURES.items()) + list(ICP_SIGNATURES.items()) + list(PLANES_SIGNATURES.items()):
+            + list(REGISTER_SIGNATURES.items()) + list(ICP_SIGNATURES.items()) + list(PLANES_SIGNATURES.items())\
+            + list(VOXEL_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args
