@@ -351,6 +351,17 @@ VOXEL_SIGNATURES = {
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/pcpx_mls.h (moving least squares projection)
+PCPX_MLS_PIVOT_MIN = 1.0 / 4096.0
+MLS_SIGNATURES = {
+    "pcpx_mls_project_self_dev": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcpx_mls_project_self": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "pcpx_mls_project_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 
 def load():
     """Load libpcpx.so; raises if it has not been built (run __graft_entry__.build())."""
@@ -367,7 +378,7 @@ def load():
             + list(SUBSAMPLE_SIGNATURES.items()) + list(SEGMENT_SIGNATURES.items()) + list(FEATURES_SIGNATURES.items())\
             + list(KEYPOINTS_SIGNATURES.items()) + list(DESCRIPTORS_SIGNATURES.items()) + list(MATCH_SIGNATURES.items())\
             + list(REGISTER_SIGNATURES.items()) + list(ICP_SIGNATURES.items()) + list(PLANES_SIGNATURES.items())\
-            + list(VOXEL_SIGNATURES.items()):
+            + list(VOXEL_SIGNATURES.items()) + list(MLS_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

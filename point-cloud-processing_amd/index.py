@@ -300,6 +300,57 @@ class Index:
         check(self._lib.pcpx_shape_features_self_dev(self._h, float(radius), first, count,
                                                      *(C.c_void_p(d) if d else None for d in (d_evals, d_curvature, d_normals, d_axes, d_counts))))
 
+    # ---- moving least squares projection (include/pcpx_mls.h) ----
+    @staticmethod
+    def _mls_outputs(rows, points, displacements, normals, curvatures, counts, fit):
+        if not (points or displacements or normals or curvatures or counts or fit):
+            raise ValueError("ask for at least one of points, displacements, normals, curvatures, counts, fit")
+        f3 = lambda want: np.empty((rows, 3), np.float32) if want else None
+        return (f3(points), f3(displacements), f3(normals), np.empty((rows, 2), np.float32) if curvatures else None,
+                np.empty(rows, np.uint32) if counts else None, np.empty(rows, np.uint32) if fit else None)
+
+    @staticmethod
+    def _mls_h(radius, gauss_h):
+        return float(np.float32(radius) / np.float32(2)) if gauss_h is None else float(gauss_h)
+
+    def mls_project_self(self, radius, gauss_h=None, order=2, points=True, displacements=False, normals=True, curvatures=False,
+                         counts=False, fit=False):
+        """Moving least squares projection of every indexed point, over every point within `radius` (itself included, the sphere of
+        range_neighbourhoods_self) with the weight exp(-d^2 / gauss_h^2): order 1 projects onto the weighted PCA plane, order 2 onto
+        a quadric fitted over that plane.  Outputs in input order: the projected points (n x 3), the displacements added to them
+        (n x 3; far from the origin they keep what float32 points round away), the surface normals (n x 3), the mean and Gaussian
+        curvature (n x 2; NaN unless fit = 2), the count (n) and the fit (n: 0 unchanged -- fewer than 3 points --, 1 plane,
+        2 quadric).  Returns the asked outputs in that order (one array alone when one is asked).
+        gauss_h defaults to radius / 2: the weight at the sphere's rim is then e^-4 (a radius of 0 needs a width of its own).  (PCL's
+        default, h = r, leaves a jump of e^-1 at the rim: a point that crosses it changes the fit at once.)"""
+        outs = self._mls_outputs(self.n_in, points, displacements, normals, curvatures, counts, fit)
+        check(self._lib.pcpx_mls_project_self(self._h, float(radius), self._mls_h(radius, gauss_h), int(order), *(_vp(o) for o in outs)))
+        return self._moments_result(outs)
+
+    def mls_project(self, queries, radius, gauss_h=None, order=2, radii=None, points=True, displacements=False, normals=True,
+                    curvatures=False, counts=False, fit=False):
+        """The same for arbitrary sphere centres `queries` (m x 3): each is projected onto the surface of the indexed cloud.  radii: one
+        radius per sphere; sphere i then uses the width gauss_h * radii[i] / radius, so `radius` (> 0) is the radius that gauss_h
+        belongs to."""
+        q = _f32(queries, 3)
+        if radii is not None:
+            radii = _f32(radii).reshape(-1)
+            if len(radii) != len(q):
+                raise ValueError("one radius per sphere")
+        outs = self._mls_outputs(len(q), points, displacements, normals, curvatures, counts, fit)
+        check(self._lib.pcpx_mls_project_batch(self._h, _vp(q), _vp(radii), float(radius), self._mls_h(radius, gauss_h), int(order), len(q),
+                                               *(_vp(o) for o in outs)))
+        return self._moments_result(outs)
+
+    def mls_project_self_dev(self, radius, gauss_h=None, order=2, d_points=None, d_displacements=None, d_normals=None, d_curvatures=None,
+                             d_counts=None, d_fit=None, first=0, count=_capi.UINT64_MAX):
+        """Device form (pointers to device arrays by input row; any may be None, not all), enqueued on the index's stream: the rows of
+        the curve positions [first, first + count) -- plus, when that is the whole order, the rows of points that are not indexed.
+        d_points is a cloud like any other: it goes straight into Index.from_device."""
+        check(self._lib.pcpx_mls_project_self_dev(self._h, float(radius), self._mls_h(radius, gauss_h), int(order), first, count,
+                                                  *(C.c_void_p(d) if d else None
+                                                    for d in (d_points, d_displacements, d_normals, d_curvatures, d_counts, d_fit))))
+
     # ---- clustering (include/pcpx_cluster.h) ----
     def cluster(self, radius, min_pts=1, compact=True, want_core=False, want_counts=False):
         """Radius-connected components (min_pts = 1) or DBSCAN of the indexed cloud: two points are joined iff one is in the other's
