@@ -14,7 +14,7 @@ OBJ_DIR = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libpcpx.so")
 SOURCES = ["pcpx_query.hip", "pcpx_few.hip", "pcpx_range.hip", "pcpx_cluster.hip", "pcpx_segment.hip", "pcpx_subsample.hip", "pcpx_keypoints.hip", "pcpx_descriptors.hip", "pcpx_match.hip", "pcpx_register.hip", "pcpx_icp.hip", "pcpx_planes.hip", "pcpx_voxel.hip", "pcpx_mls.hip", "pcpx_filter.hip", "pcpx_normals.hip", "pcpx_prep.hip", "pcpx_orient.hip", "pcpx_build.hip", "pcpx_shard.hip", "pcpx_sort.hip",
            "pcpx_comm.hip", "pcpx_kd.hip", "pcpx_isosurface.hip", "pcpx_simplify.hip", "pcpx_runtime.hip", "pcpx_api.hip"]
-HEADERS = [os.path.join(CSRC, "pcpx_internal.h"), os.path.join(CSRC, "pcpx_device.h"), os.path.join(CSRC, "pcpx_box_bound.h"), os.path.join(CSRC, "pcpx_eig3.h"), os.path.join(CSRC, "pcpx_curve.h"),
+HEADERS = [os.path.join(CSRC, "pcpx_internal.h"), os.path.join(CSRC, "pcpx_device.h"), os.path.join(CSRC, "pcpx_box_bound.h"), os.path.join(CSRC, "pcpx_path_start.h"), os.path.join(CSRC, "pcpx_eig3.h"), os.path.join(CSRC, "pcpx_curve.h"),
            os.path.join(CSRC, "pcpx_curve_table.h"), os.path.join(CSRC, "pcpx_scan.h"), os.path.join(CSRC, "pcpx_unionfind.h"), os.path.join(CSRC, "pcpx_labels.h"), os.path.join(CSRC, "pcpx_keep.h"), os.path.join(CSRC, "pcpx_stage.h"), os.path.join(CSRC, "pcpx_lease.h"), os.path.join(CSRC, "pcpx_horn.h"), os.path.join(CSRC, "pcpx_plane_solve.h"), os.path.join(CSRC, "pcpx_ransac.h"), os.path.join(CSRC, "pcpx_fixed_sum.h"), os.path.join(CSRC, "pcpx_plane_fit.h"),
            os.path.join(INCLUDE, "pcpx.h"), os.path.join(INCLUDE, "pcpx_radius.h"), os.path.join(INCLUDE, "pcpx_cluster.h"),
            os.path.join(INCLUDE, "pcpx_subsample.h"), os.path.join(INCLUDE, "pcpx_segment.h"), os.path.join(INCLUDE, "pcpx_features.h"),

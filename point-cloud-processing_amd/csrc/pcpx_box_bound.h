@@ -52,6 +52,29 @@ constexpr float BOX_BOUND_K = 1.f + 0x1p-20f;
 
 PCPX_BOX_BOUND_FN float box_bound_tau(float tau) { return tau * BOX_BOUND_K + FLT_MIN; }
 
+// The same bound from a box U to a whole box W of queries (k_knn's path start, WalkerT::start_path: W = the tight box of a wave's 64
+// queries, tau = the round's cap, which no lane's tau exceeds):
+//
+//     box_gap_bound_fused(U, W) <= box_bound_tau(cap)   whenever some p in U and q in W have reference d2(p, q) <= cap.
+//
+// The argument above carries over with g_a = max(fl(lo_U - hi_W), fl(lo_W - hi_U), 0) in the place of the axis distance d_a:
+//   * lo_U <= p_a and q_a <= hi_W give lo_U - hi_W <= p_a - q_a in the reals, and rounding is monotone: fl(lo_U - hi_W) <= e_a;
+//     likewise fl(lo_W - hi_U) <= fl(q_a - p_a) = -e_a.  So g_a <= |e_a| on every axis -- the only property of d_a the argument uses
+//     -- and F = fused(g) <= fused(|e|) = F' < R (1 + 5.1 u) < box_bound_tau(R) <= box_bound_tau(cap), box_bound_tau being monotone.
+//   * For any one query q in W, g_a <= d_a(U, q) as well (q_a <= hi_W, lo_W <= q_a): the value never exceeds box_bound_fused(U, q), so
+//     a box this test drops is one the per-lane test drops for every lane whose tau is within the cap.
+// Edges as above: cap = +inf passes every real box (the gaps of finite boxes are finite or overflow to +inf, and +inf <= +inf);
+// cap = 0 becomes FLT_MIN, and touching or overlapping boxes give 0; U's NaN `poison` makes the value NaN: the test fails.
+// W needs lo(axis) and hi(axis) only.
+template <class Box, class QueryBox>
+PCPX_BOX_BOUND_FN float box_gap_bound_fused(const Box& u, const QueryBox& w)
+{
+    const float gx = fmaxf(fmaxf(u.lo(0) - w.hi(0), w.lo(0) - u.hi(0)), 0.f);
+    const float gy = fmaxf(fmaxf(u.lo(1) - w.hi(1), w.lo(1) - u.hi(1)), 0.f);
+    const float gz = fmaxf(fmaxf(u.lo(2) - w.hi(2), w.lo(2) - u.hi(2)), 0.f);
+    return __builtin_fmaf(gz, gz, __builtin_fmaf(gy, gy, __builtin_fmaf(gx, gx, u.poison)));
+}
+
 }  // namespace pcpx
 
 #undef PCPX_BOX_BOUND_FN

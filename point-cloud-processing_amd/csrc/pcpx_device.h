@@ -5,6 +5,8 @@
 #define PCPX_DEVICE_H
 
 #include "pcpx_internal.h"
+#include "pcpx_box_bound.h"
+#include "pcpx_path_start.h"
 
 #include <cmath>
 #include <limits>
@@ -120,6 +122,13 @@ __device__ __forceinline__ u32 lds_address(const void* p)
 
 // ---- wave-uniform walk over the implicit 4-ary tree ------------------------------------------------
 
+// the tight box of a wave's queries (WalkerT::start_path)
+struct QueryBox {
+    float lo3[3], hi3[3];
+    __device__ float lo(int a) const { return lo3[a]; }
+    __device__ float hi(int a) const { return hi3[a]; }
+};
+
 // All members are wave-uniform (SGPRs).  next() yields, in curve (= sorted) order, every leaf whose box is still
 // needed by at least one lane at the time its parent is expanded.  State: bit 4*h + c of `pend` = child c
 // (a node of height h; leaves have height 0) of the current ancestor of height h+1 is still to visit.  A
@@ -188,6 +197,62 @@ struct WalkerT {
         l2 = __builtin_amdgcn_readfirstlane(2u * static_cast<u32>(l));  // (or hipcc carries it round k_knn's walk in a vector register)
         pend = static_cast<u64>(child_mask(t, 0, 0u, need)) << (W * l);
         return false;
+    }
+
+    // The start of a SELF group's round (k_knn): one step of the wave in the place of the root test and the depth - 1 expansions of the
+    // group's own ancestors, whose outcome is known -- every lane's own point lies inside them (pcpx_path_start.h: the lanes' nodes,
+    // the start state).  In two pieces:
+    //   path_fetch   each lane loads the box of its node (vector loads); the group's own two last-level nodes -- together the tight box
+    //                of its 64 queries, the WAVE BOX -- come as scalar loads.  (A piece of its own so that a caller with registers to
+    //                spare can fetch ahead of the round; k_knn has none -- eight VGPRs held across wave_radius_cap put its k <= 16
+    //                kernels into scratch -- and fetches where the round starts: profiles/experiments/README.md);
+    //   start_path   a lane's node passes if its box-to-box bound to the wave box is within the slackened `cap`
+    //                (box_gap_bound_fused, pcpx_box_bound.h).  cap = the round's wave-uniform cap: every searching lane's tau is at most
+    //                that from the end of the seed phase on and only shrinks, so the one test covers every lane for the whole round.
+    // The test is conservative for the lanes (a passing sibling need not be needed by any: popped, its exact expansion then yields an
+    // empty mask) and nothing is dropped that a lane needs.  The walk then runs as from start(), from inside the height-2 ancestor:
+    // first that node's other children, then the ancestors' siblings, upwards.  Depth 0: no lane stands for a node, pend = 0.
+    struct PathBoxes {
+        NodeBox mine;      // per lane
+        NodeBox own[2];    // wave-uniform: last-level nodes 2 g and 2 g + 1 (the second may be a padding node)
+        u64 lanes;         // the lanes that stand for a node to test
+    };
+    static __device__ __forceinline__ PathBoxes path_fetch(const TreeView& t, const u32 g, u32 lane)
+    {
+        asm volatile("" : "+v"(lane));  // (opaque: what depends on the lane alone is otherwise kept in registers from group to group)
+        const u32 depth = static_cast<u32>(t.depth);
+        const PathLane pl = path_lane(lane, g, depth, 30u - 2u * depth);
+        PathBoxes pb;
+        pb.lanes = __builtin_amdgcn_ballot_w64(pl.on);
+        // (global address space: a load through the generic pointer is a flat one, which the scalar loads below would wait for)
+        typedef float f32x4 __attribute__((ext_vector_type(4)));
+        typedef const __attribute__((address_space(1))) f32x4* global_f32x4_ptr;
+        const global_f32x4_ptr mine = (global_f32x4_ptr)(reinterpret_cast<uintptr_t>(t.nodes + pl.node));
+        const f32x4 a = mine[0], b = mine[1];
+        pb.mine.set(a.x, a.y, a.z, a.w, b.x, b.y);
+        pb.mine.poison = b.z;
+        pb.mine.pad = 0.f;
+        const u32 own0 = depth != 0u ? level_base(t.depth - 1) + 2u * g : 0u;  // (depth 0: the root, read and not used)
+        pb.own[0] = load_const(t.nodes + own0);
+        pb.own[1] = load_const(t.nodes + own0 + (depth != 0u ? 1u : 0u));
+        return pb;
+    }
+    __device__ __forceinline__ void start_path(const TreeView& t, const u32 g, const PathBoxes& pb, const float cap)
+    {
+        lshift0 = static_cast<u32>(30 - 2 * t.depth);
+        asm("" : "+s"(lshift0));  // (as in start())
+        ploc = g >> 1;
+        l = 1;
+        l2 = 2;
+        // the wave box: the union of the group's own last-level nodes (a real node's poison is +0, all bits clear)
+        QueryBox w;
+        const bool two = __float_as_uint(pb.own[1].poison) == 0u;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            w.lo3[a] = two ? fminf(pb.own[0].lo(a), pb.own[1].lo(a)) : pb.own[0].lo(a);
+            w.hi3[a] = two ? fmaxf(pb.own[0].hi(a), pb.own[1].hi(a)) : pb.own[0].hi(a);
+        }
+        pend = __builtin_amdgcn_ballot_w64(box_gap_bound_fused(pb.mine, w) <= box_bound_tau(cap)) & pb.lanes;
     }
 
     // The same walk as next(), in pieces, for a caller that keeps "is there another leaf" in its control flow instead of in

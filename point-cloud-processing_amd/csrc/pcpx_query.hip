@@ -835,7 +835,8 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
 
     // ---- walk rounds ----
     constexpr bool packed_leaves = pack_rows(MULTI, KCAP) > 0 && fast && !EPS_EACH;  // (wants the lanes that need each leaf: WalkerT's KEEP)
-    WalkerT<(KCAP > 8), packed_leaves> wk;
+    using WalkerK = WalkerT<(KCAP > 8), packed_leaves>;
+    WalkerK wk;
     // A leaf of the walk that at most PACKED_LEAVES lanes need (three quarters of the walk's leaves: the lane-per-query form
     // computes 512 distances there of which 8 ... 192 matter) is looked at EIGHT NEEDING LANES x EIGHT POINTS at a time: the
     // needing lanes publish {query, tau} and their write address in LDS in the order of their rank (v_mbcnt of the need mask);
@@ -944,8 +945,15 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
         // (wave-uniform as it is, but carried round a loop whose exit hipcc takes for lane-dependent -- `cap` comes out of lane exchanges --
         //  it counts as a vector value, and a scalar flag made from it is an "illegal VGPR to SGPR copy")
         const u32 packed_limit_now = __builtin_amdgcn_readfirstlane(packed_limit);
-        bool root_leaf = wk.start(t, need, st_expand);
-        (void)root_leaf;  // depth 0: the only leaf is the seed chunk, already done
+        // A self group starts inside the height-2 ancestor of its own points, with the siblings of its ancestors pending that the
+        // wave's box is within the cap of (one step of the wave: WalkerT::start_path); a batch group starts at the root.
+        if (SELF) {
+            wk.start_path(t, g, WalkerK::path_fetch(t, g, lane), cap);
+            ++st_expand;
+        } else {
+            bool root_leaf = wk.start(t, need, st_expand);
+            (void)root_leaf;  // depth 0: the only leaf is the seed chunk, already done
+        }
         // A trip of the outer loop pops one node and expands it (WalkerT::expand_any: one copy of the expansion for every height); a
         // LAST-LEVEL node hands its needed leaves to the inner loop directly (no trip through the pending bits for them -- a dozen scalar
         // instructions per leaf, and the scalar side of this kernel is what it is short of); `direct` = its children still to look
