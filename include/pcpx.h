@@ -36,6 +36,10 @@
  *     the caller's other default-stream work), never a private one.  The others take HOST pointers and are
  *     synchronous; they run on a stream of their own.  Every entry point restores the calling thread's
  *     current device before it returns.
+ *   - Device pointers need only their element type's alignment (4 bytes for float / uint32_t, 8 for uint64_t / double, 1 for
+ *     uint8_t): a slice of a larger array is a legal argument.  kNN outputs that are 16-byte aligned, with a pitch of 8 / 16 /
+ *     32 entries, get the single-store row form (pcpx_knn_self_strided_dev); any other address gets the same bits by narrower stores.
+ *   - A call writes only inside the documented extents of its outputs.
  *   - There is no CPU fallback: without a usable HIP device every compute entry point fails
  *     with PCPX_ERR_DEVICE.
  */
@@ -164,7 +168,7 @@ int pcpx_knn_batch_dev(pcpx_index* idx, const float* d_q_xyz, uint64_t nq, uint3
  * k .. row_stride of every answered row are 0xFFFFFFFF / +inf, rows of the other points are left untouched).  The reference
  * returns one std::vector per query (include/pcp/octree/linked_octree.hpp:245-254), so the row pitch is this library's to
  * choose: with row_stride = 16 (k = 15 or 16; 8 for k = 7, 8; 32 for k = 31, 32) and outputs aligned to 16 bytes a row is ONE
- * aligned 64-byte piece, written with 16-byte stores.  Packed 60-byte rows scattered by input index cost every partial 32-byte
+ * aligned 64-byte piece, written with 16-byte stores (outputs that are not: the same rows, word by word).  Packed 60-byte rows scattered by input index cost every partial 32-byte
  * sector twice at the memory side (read for ownership + write back): 1.57 GB written per 10 M queries for 0.76 GB of payload
  * (profiles/r04_hbm_traffic.json). */
 int pcpx_knn_self_strided_dev(pcpx_index* idx, uint32_t k, float eps, uint64_t sorted_first, uint64_t sorted_count,
@@ -427,7 +431,8 @@ int pcpx_debug_set(pcpx_index* idx, const char* name, int64_t value);
  * "full_buckets" (top-digit buckets that take every radix pass since), "schedule_state" (0: nothing recorded, 1: group times
  * recorded, 2: the recorded order is in use), "poisoned_bytes" (what the handle's last "poison" filled in all),
  * "poisoned_shared_bytes" (of that, in the device's pool and its finished leases), "poisoned_cache_bytes" (of that, in the idle
- * index blocks), "scratch_bytes" (the size of the handle's scratch block now). */
+ * index blocks), "scratch_bytes" (the size of the handle's scratch block now), "knn_row_form" (how the handle's last k <= 32 kNN launch
+ * that wrote index or distance rows stored them: 1 = whole rows of 8 / 16 / 32 entries as 16-byte stores, 0 = word by word). */
 int pcpx_debug_get(pcpx_index* idx, const char* name, int64_t* out_value);
 /* What the handle's last recorded self-kNN launch took per query group (shader-clock ticks / 64, search only; host array of
  * *out_groups entries, the launch's groups in curve order; 0 groups: nothing recorded).  PCPX_ERR_CAPACITY reports the size. */

@@ -1101,6 +1101,8 @@ int pcpx_debug_get(pcpx_index* h, const char* name, int64_t* out_value)
         *out_value = static_cast<int64_t>(ix->poisoned_cache_bytes);
     } else if (key == "scratch_bytes") {
         *out_value = static_cast<int64_t>(ix->scratch_bytes);
+    } else if (key == "knn_row_form") {
+        *out_value = ix->knn_row_form;
     } else {
         set_error("pcpx_debug_get: no figure called '%s'", name);
         return PCPX_ERR_INVALID;

@@ -105,6 +105,9 @@ struct KnnOutputs {
     u32 row_stride = 0;         // entries between the rows of idx / d2 (0: k).  A stride of KCAP (8 / 16 / 32) with k = KCAP or KCAP - 1
                                 // makes a row one aligned piece written with 16-byte stores: a 60-byte row scattered by input index
                                 // costs its partial 32-byte sectors twice (read for ownership + write back)
+    u32 rows16 = 0;             // set by the launcher (launch_knn_form), never by a caller: idx and d2 are both 16-byte aligned (null counts
+                                // as aligned), so a row of KCAP entries may leave as 16-byte stores; 0: word by word, the same bits --
+                                // a device pointer owes its element type's alignment and no more (include/pcpx.h)
     float4* nc4 = nullptr;      // self queries: {normal, count as bits} of sorted position p at [p] INSTEAD of normals / cnt by row -- the
                                 // first half of the gather-form permute to input order (k_gather_nc4: coalesced writes, cached reads)
 };
@@ -204,6 +207,7 @@ struct Index {
     const u32* finish_first_pass = nullptr;  // ... and its per-bucket table
     u32 full_buckets[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // top-digit buckets that take every radix pass (a build found a run it could not order in LDS)
     u32 build_redos = 0;                   // builds that were repeated because of that (diagnostic)
+    u32 knn_row_form = 0;                  // the last k_knn launch that wrote rows: 1 = whole rows as 16-byte stores, 0 = word by word (diagnostic)
     u32 low_pass_tiles = ~0u;              // tiles the sort's two lowest passes had in the last build (~0: no build yet): sizes their grids next time
     void* d_sort_tmp = nullptr;
     size_t sort_tmp_bytes = 0;

@@ -228,7 +228,8 @@ __global__ __launch_bounds__(MT_BLOCK) void k_match_compact(u32 m, const uint8_t
     const u32 i = blockIdx.x * MT_BLOCK + threadIdx.x;
     if (i >= m || !keep[i]) return;
     const u32 at = place[i];
-    reinterpret_cast<uint2*>(out_pairs)[at] = uint2{i, best_idx[i]};
+    out_pairs[2ull * at] = i;  // (two words: the caller's array is only 4-byte aligned, include/pcpx.h)
+    out_pairs[2ull * at + 1] = best_idx[i];
     if (out_d2) out_d2[at] = best_d2[i];
 }
 

@@ -1105,7 +1105,9 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
             // (high bits, for diagnosis -- pcpx_shard_cuts_by_cost masks them off: walk rounds after the first, and the lanes they ran for)
             e.x = st_expand, e.y = (st_leaves & 0xFFFFFFu) | (st_round2 << 24), e.z = (st_sparse & 0xFFFFFu) | ((st_later_lanes < 0xFFFu ? st_later_lanes : 0xFFFu) << 20),
             e.w = (st_compact << 16) | (st_steps < 0xFFFFu ? st_steps : 0xFFFFu);
-            reinterpret_cast<uint4*>(events)[slot] = e;
+            // (four words: the caller's array is only 4-byte aligned, include/pcpx.h; one lane per group, a diagnostic launch)
+            u32* const at = events + 4ull * slot;
+            at[0] = e.x, at[1] = e.y, at[2] = e.z, at[3] = e.w;
         }
     }
     const int first_slot = KCAP - static_cast<int>(k);
@@ -1221,7 +1223,10 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
     // (read for ownership, write back), and a store instruction of 64 lanes touches 64 lines whatever its width.
     // (NZ = 1: the kernel for k < KCAP, whose slot 0 holds the sentinel: k = KCAP - 1 is the shift by one; NZ = 0: k = KCAP in the
     //  deferred-eps kernels, any k in the per-candidate ones)
-    const bool whole_rows = stride == static_cast<u32>(KCAP) && first_slot == NZ && !STATS;
+    // Only where both arrays are 16-byte aligned (KnnOutputs::rows16, the launcher's look at the two addresses: a pitch of KCAP words
+    // keeps every row as aligned as its array): a caller owes its element type's alignment and no more (include/pcpx.h), and gets the
+    // same bits word by word.
+    const bool whole_rows = stride == static_cast<u32>(KCAP) && first_slot == NZ && !STATS && o.rows16 != 0;
     auto store_whole_rows = [&](auto FS) {
         constexpr int fs = decltype(FS)::value;
 #pragma unroll
@@ -1621,8 +1626,8 @@ static int launch_knn_form(Index& ix, const QueryView& qv, u64 gfirst, u64 gcoun
     constexpr int WPB = knn_wpb(KCAP, false);
     const size_t lds = static_cast<size_t>(WPB) * lds_rows(BUF, false, KCAP) * 64 * sizeof(u64);
     const u32 gf = static_cast<u32>(gfirst), ge = static_cast<u32>(gfirst + gcount);
-    if (o.row_stride != 0 && (o.row_stride < k || ((o.row_stride == static_cast<u32>(KCAP)) && ((reinterpret_cast<uintptr_t>(o.idx) | reinterpret_cast<uintptr_t>(o.d2)) & 15u) != 0))) {
-        set_error("pcpx: row_stride must be >= k, and rows of %d entries must start at multiples of 16 bytes", KCAP);
+    if (o.row_stride != 0 && o.row_stride < k) {  // (rows at any address: the row form below follows the arrays' alignment)
+        set_error("pcpx: row_stride must be >= k");
         return PCPX_ERR_INVALID;
     }
     int st = prepare_queue(ix);
@@ -1645,7 +1650,12 @@ static int launch_knn_form(Index& ix, const QueryView& qv, u64 gfirst, u64 gcoun
         }
     }
     ProfileScope prof(ix, PCPX_K_KNN);
-    fn<<<pgrid, 64 * WPB, lds, ix.stream>>>(KnnArgs{ix.view(), qv, gf, ge, k, eps, thr, o, MultiPass{}, ix.queue_now, nullptr, sch, ix.queue_clear});
+    // the row form (the kernel's epilogue): whole rows as 16-byte stores need a pitch of KCAP, k = KCAP - NZ and 16-byte aligned arrays
+    KnnOutputs out = o;
+    out.rows16 = ((reinterpret_cast<uintptr_t>(o.idx) | reinterpret_cast<uintptr_t>(o.d2)) & 15u) == 0 ? 1u : 0u;
+    if (o.idx || o.d2)
+        ix.knn_row_form = (o.row_stride ? o.row_stride : k) == static_cast<u32>(KCAP) && KCAP - static_cast<int>(k) == NZ && out.rows16 ? 1u : 0u;
+    fn<<<pgrid, 64 * WPB, lds, ix.stream>>>(KnnArgs{ix.view(), qv, gf, ge, k, eps, thr, out, MultiPass{}, ix.queue_now, nullptr, sch, ix.queue_clear});
     return check_hip(hipGetLastError(), "k_knn launch", __FILE__, __LINE__);
 }
 

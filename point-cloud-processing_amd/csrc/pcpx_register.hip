@@ -69,7 +69,7 @@ struct Pairs {
     // the six coordinates of correspondence k (k below the capacity); false when it is not usable
     __device__ __forceinline__ bool load(u32 k, float (&x)[6]) const
     {
-        const uint2 st = reinterpret_cast<const uint2*>(pairs)[k];
+        const uint2 st{pairs[2ull * k], pairs[2ull * k + 1]};  // (two words: the caller's array is only 4-byte aligned, include/pcpx.h)
         if (st.x >= np || st.y >= nq) return false;
         bool finite = true;
 #pragma unroll

@@ -771,7 +771,7 @@ class Index:
 
     def debug_get(self, name):
         """pcpx_debug_get: 'build_redos', 'full_buckets', 'schedule_state', 'poisoned_bytes', 'poisoned_shared_bytes', 'poisoned_cache_bytes',
-        'scratch_bytes'."""
+        'scratch_bytes', 'knn_row_form'."""
         v = C.c_int64(0)
         check(self._lib.pcpx_debug_get(self._h, name.encode(), C.byref(v)))
         return int(v.value)
