@@ -227,14 +227,23 @@ struct WalkerT {
         // (global address space: a load through the generic pointer is a flat one, which the scalar loads below would wait for)
         typedef float f32x4 __attribute__((ext_vector_type(4)));
         typedef const __attribute__((address_space(1))) f32x4* global_f32x4_ptr;
-        const global_f32x4_ptr mine = (global_f32x4_ptr)(reinterpret_cast<uintptr_t>(t.nodes + pl.node));
+        // (the node's byte offset as two opaque words: widened as `t.nodes + pl.node`, hipcc keeps the pair {number, 0} in two VGPRs from
+        //  group to group of the persistent kernel, and k_knn's k <= 16 kernels have none to spare -- it went to scratch)
+        static_assert(sizeof(NodeBox) == 32, "the shifts below");
+        u32 off_lo = pl.node << 5, off_hi = pl.node >> 27;
+        asm volatile("" : "+v"(off_lo), "+v"(off_hi));
+        const global_f32x4_ptr mine = (global_f32x4_ptr)(reinterpret_cast<uintptr_t>(t.nodes) + ((static_cast<u64>(off_hi) << 32) | off_lo));
         const f32x4 a = mine[0], b = mine[1];
         pb.mine.set(a.x, a.y, a.z, a.w, b.x, b.y);
         pb.mine.poison = b.z;
         pb.mine.pad = 0.f;
         const u32 own0 = depth != 0u ? level_base(t.depth - 1) + 2u * g : 0u;  // (depth 0: the root, read and not used)
-        pb.own[0] = load_const(t.nodes + own0);
-        pb.own[1] = load_const(t.nodes + own0 + (depth != 0u ? 1u : 0u));
+        // (both numbers opaque scalars, formed where the round starts: the second one's address is otherwise formed in a VGPR pair ahead of
+        //  the rounds and kept -- in scratch, in the k <= 16 kernels -- for a later round that hardly any group has)
+        u32 own_a = own0, own_b = own0 + (depth != 0u ? 1u : 0u);
+        asm volatile("" : "+s"(own_a), "+s"(own_b));
+        pb.own[0] = load_const(t.nodes + own_a);
+        pb.own[1] = load_const(t.nodes + own_b);
         return pb;
     }
     __device__ __forceinline__ void start_path(const TreeView& t, const u32 g, const PathBoxes& pb, const float cap)

@@ -144,7 +144,7 @@ __device__ __forceinline__ void bitonic_merge(u64 (&a)[N])
 constexpr int BUF8 = 10;   // k <= 8: 10 rows x 512 B = 5 KB per wave, 8 waves/SIMD
 constexpr int BUF16 = 10;  // 10 rows x 512 B = 5 KB per wave = 7 waves/SIMD
 constexpr int BUF32 = 14;  // (+ 2 rows of LDS that only the epilogue uses: lds_rows)
-constexpr int SEED_DIRECT = 8;     // largest KCAP whose seed leaves skip the append buffer (k <= 16 / 32: scratch in the seed phase)
+constexpr int SEED_DIRECT = 16;    // largest KCAP whose seed leaves skip the append buffer (k <= 16: in a loop of their own, knn_group: direct_seed_loop; k <= 32: the list alone is 64 of 128 registers)
 constexpr int PACKED_LEAVES = 24;  // a walk leaf that 2 ... this many lanes need is looked at eight needing lanes x eight points at a time
 constexpr int PACKED_FREE16 = 3;   // k <= 16 kernel: free rows every needing lane has when a packed leaf starts.  The k <= 32 kernel always waits for LEAF rows, like the other forms -- no key can then find its column full: its fold is twice the network, and what the optimistic fill loses there it does not win back (measured)
 // Wave priorities (s_setprio) by phase of a group.  A fold is ~130 vector instructions back to back that wait for nothing; the
@@ -797,7 +797,14 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
     // (the same best-list as accepting them one by one: a key beyond tau falls off its end).  Not for the cloud's last leaf
     // (its padding slots are NaN, which the compare-exchange network cannot carry) and not in the per-candidate eps form.
     constexpr bool direct_seeds = KCAP <= SEED_DIRECT && chunked_compaction(MULTI) && !EPS_EACH && !STATS;
-    auto seed_direct = [&](const u32 leaf) {
+    // k <= 8: a direct leaf is a branch of the seed loop below.  k <= 16: the direct leaves run in a straight loop of their own in
+    // front of it, which then only sees what is left (the cloud's last leaf) -- as a branch of the shared loop the form put the
+    // k <= 16 kernels into 28 ... 108 B of scratch, three times over.  Not in the event-counting build: what it counts per seed leaf
+    // is the buffered form's fold, which is due when a lane holds three keys -- nearly always, and a direct leaf cannot tell when
+    // not; its list after the seed phase, and so its walk, is the same either way.
+    constexpr bool direct_in_seed_loop = direct_seeds && KCAP <= 8;
+    constexpr bool direct_seed_loop = direct_seeds && KCAP > 8 && !COST;
+    auto seed_merge = [&](const u32 leaf) {
         const Leaf lf = load_const(t.leaves + leaf);
         const u32 posbase = leaf * LEAF;
         u64 nw[LEAF];
@@ -813,14 +820,30 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
 #pragma unroll
         for (int j = 0; j < LEAF; ++j) best[KCAP - 1 - j] = key_min(best[KCAP - 1 - j], nw[j]);
         bitonic_merge<KCAP, NZ, LEAF>(best);
+    };
+    auto seed_direct = [&](const u32 leaf) {
+        seed_merge(leaf);
         tau = active ? fminf(__uint_as_float(static_cast<u32>(best[KCAP - 1] >> 32)), cap) : -1.f;
         tau_slack = box_bound_tau(tau);
     };
+    u32 seed_from = s0;
+    if (direct_seed_loop) {
+        // every seed leaf but the cloud's last, in curve order.  Nothing in here reads tau: it is formed once, behind the loop.  The
+        // list is made opaque between two leaves, so that hipcc does not carry pieces of one leaf's merge into the next one's keys.
+        const u32 direct_end = s1 - ((s1 == t.nleaves && s1 > s0) ? 1u : 0u);  // (s1 > s0: an empty range stays empty, also in a tree without leaves)
+        for (; seed_from < direct_end; ++seed_from) {
+            seed_merge(seed_from);
+#pragma unroll
+            for (int j = 0; j < KCAP; ++j) asm volatile("" : "+v"(best[j]));
+        }
+        tau = active ? fminf(__uint_as_float(static_cast<u32>(best[KCAP - 1] >> 32)), cap) : -1.f;
+        tau_slack = box_bound_tau(tau);
+    }
     // (the seed leaves from the middle of the range outwards instead of in curve order -- the middle of the group's own chunk is near
     //  most of its lanes -- was measured in round 4: no gain; profiles/experiments/README.md)
-    for (u32 leaf = s0;; ++leaf) {
+    for (u32 leaf = seed_from;; ++leaf) {
         const bool more = leaf < s1;
-        if (direct_seeds && more && leaf + 1u != t.nleaves) {
+        if (direct_in_seed_loop && more && leaf + 1u != t.nleaves) {
             seed_direct(leaf);
             continue;
         }
@@ -1118,7 +1141,9 @@ __device__ __forceinline__ void knn_group(const TreeView& tree, const u32 g, con
     // gets a lane mask or a scalar select of its own, and KCAP of them at once spill.
     if (!SELF) {
         const knn_args_ptr kq = knn_args_here();
-        u32 pq = g * GROUP + lane;
+        u32 lane_q = lane;
+        asm volatile("" : "+v"(lane_q));  // (formed from an opaque lane: or it is the group start's g * GROUP + lane, kept -- in scratch -- through the search)
+        u32 pq = g * GROUP + lane_q;
         asm volatile("" : "+v"(pq));
         float x = 0.f, y = 0.f, z = 0.f;
         if (valid) {
