@@ -362,6 +362,17 @@ MLS_SIGNATURES = {
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/pcpx_outliers.h (outlier removal: resolution, statistical, radius, density)
+PCPX_OUTLIERS_ON_DEVICE = 1
+OUTLIERS_SIGNATURES = {
+    "pcpx_outliers_resolution_self": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "pcpx_outliers_statistical_self": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]),
+    "pcpx_outliers_radius_self": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcpx_outliers_density_self": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 
 def load():
     """Load libpcpx.so; raises if it has not been built (run __graft_entry__.build())."""
@@ -378,7 +389,7 @@ def load():
             + list(SUBSAMPLE_SIGNATURES.items()) + list(SEGMENT_SIGNATURES.items()) + list(FEATURES_SIGNATURES.items())\
             + list(KEYPOINTS_SIGNATURES.items()) + list(DESCRIPTORS_SIGNATURES.items()) + list(MATCH_SIGNATURES.items())\
             + list(REGISTER_SIGNATURES.items()) + list(ICP_SIGNATURES.items()) + list(PLANES_SIGNATURES.items())\
-            + list(VOXEL_SIGNATURES.items()) + list(MLS_SIGNATURES.items()):
+            + list(VOXEL_SIGNATURES.items()) + list(MLS_SIGNATURES.items()) + list(OUTLIERS_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

@@ -430,6 +430,13 @@ int launch_knn_few(Index& ix, const float* q_aos, const float* q_host, u32 nq, u
 int launch_knn_stats(Index& ix, u32 k, float eps, unsigned long long* d_stats, const float* d_known_d2 = nullptr);
 int launch_range_count(Index& ix, const QueryView& qv, bool self, u64 group_first, u64 group_count, float radius,
                        const float* d_radii, u32* d_out_cnt);
+// the self count form with the radius a float in device memory (pcpx_outliers.hip: the radius never visits the host)
+int launch_range_count_self_radius_at(Index& ix, const QueryView& qv, u64 group_first, u64 group_count, const float* d_radius,
+                                      u32* d_out_cnt);
+// the at-least form of the self count walk: d_keep[row] = the sphere holds at_least (>= 1) points; the radius is `radius`, or the
+// float at d_radius when that is not null
+int launch_range_at_least_self(Index& ix, const QueryView& qv, u64 group_first, u64 group_count, float radius, const float* d_radius,
+                               u32 at_least, uint8_t* d_keep);
 int launch_range_fill(Index& ix, const QueryView& qv, float radius, const float* d_radii, const u64* d_offsets,
                       u32* d_out_idx);
 int launch_range_offsets(Index& ix, const u32* d_cnt, u64 n_rows, u64* d_tile_sum, u64* d_offsets);

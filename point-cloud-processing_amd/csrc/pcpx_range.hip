@@ -78,13 +78,20 @@ struct MomentsOut {
     float* mean_dist = nullptr;  // rows
     u32* count = nullptr;        // rows
 };
-template <bool SELF, bool FILL, int MOM = 0>
+
+// AT_LEAST (the outlier filters of pcpx_outliers.hip; count form only): the caller asks only whether the sphere holds `at_least`
+// points.  A lane whose count has reached the bound stops needing nodes: its r^2 becomes the idle lane's -1, so it passes no further
+// distance test, asks for no further box and publishes -1 in the packed leaves it was already booked for.  A lane that never
+// reaches the bound has walked its whole sphere.  It writes keep = count >= at_least by input row and no count.
+template <bool SELF, bool FILL, int MOM = 0, bool AT_LEAST = false>
 __device__ __forceinline__ void range_group(const TreeView& t, const QueryView& qv, const u32 g, const float radius,
                                             const float* __restrict__ radii, u32* __restrict__ out_cnt,
                                             const u64* __restrict__ offsets, u32* __restrict__ out_idx, float4* __restrict__ pub,
-                                            const u32 lane, const MomentsOut mo = MomentsOut{}, const FeaturesOut fo = FeaturesOut{})
+                                            const u32 lane, const MomentsOut mo = MomentsOut{}, const FeaturesOut fo = FeaturesOut{},
+                                            const u32 at_least = 0u, uint8_t* __restrict__ keep_out = nullptr)
 {
     static_assert(MOM == 0 || !FILL, "the moments form lists nothing");
+    static_assert(!AT_LEAST || (MOM == 0 && !FILL), "the at-least form is a count form");
     const u32 p = g * GROUP + lane;
     const u32 nq = SELF ? t.n : qv.nq;
     const bool valid = p < nq && (!SELF || p - qv.pos_lo < qv.pos_hi - qv.pos_lo);  // (self ranges: only the asked positions)
@@ -94,7 +101,7 @@ __device__ __forceinline__ void range_group(const TreeView& t, const QueryView& 
     const u32 row = q.row;
     float r = radius;
     if (radii && valid) r = radii[row];
-    const float r2 = valid ? r * r : -1.f;  // sphere.hpp:34 radius * radius in float; -1: idle lane
+    float r2 = valid ? r * r : -1.f;  // sphere.hpp:34 radius * radius in float; -1: idle lane (only the at-least form writes it again)
     __builtin_amdgcn_s_setprio(PRIO_BASE);
     u32 cnt = 0;
     u64 wpos = (FILL && valid) ? offsets[row] : 0;
@@ -138,6 +145,9 @@ __device__ __forceinline__ void range_group(const TreeView& t, const QueryView& 
                 : "s"(inside[0]), "s"(inside[1]), "s"(inside[2]), "s"(inside[3]), "s"(inside[4]), "s"(inside[5]), "s"(inside[6]),
                   "s"(inside[7]));
             __builtin_amdgcn_s_setprio(PRIO_BASE);
+            if constexpr (AT_LEAST) {
+                if (cnt >= at_least) r2 = -1.f;
+            }
             return;
         }
 #pragma unroll
@@ -191,6 +201,9 @@ __device__ __forceinline__ void range_group(const TreeView& t, const QueryView& 
         __builtin_amdgcn_wave_barrier();
         if (mine) reinterpret_cast<float*>(pub + rank)[3] = -1.f;
         __builtin_amdgcn_wave_barrier();
+        if constexpr (AT_LEAST) {
+            if (cnt >= at_least) r2 = -1.f;
+        }
     };
     walk_needed_leaves<packed_leaves>(t, need, [&](const u32, const Leaf* record, const u64 who, const u32 how_many) {
         if (packed_leaves && how_many <= PACKED_LEAVES) packed_leaf(record, who, how_many);
@@ -227,6 +240,8 @@ __device__ __forceinline__ void range_group(const TreeView& t, const QueryView& 
         }
         if (MOM == 2 && mo.mean_dist) mo.mean_dist[row] = dsum / fn;
         if (mo.count) mo.count[row] = cnt;
+    } else if constexpr (AT_LEAST) {
+        if (valid) keep_out[row] = cnt >= at_least ? 1 : 0;
     } else {
         if (valid && !FILL) out_cnt[(SELF && qv.by_position) ? p + qv.pos_bias : row] = cnt;
     }
@@ -246,6 +261,37 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void k_range(TreeView t, Quer
     if (g >= group_end) return;
     if (lane < 32u) published[wave_in_block()][lane].w = -1.f;  // packed_leaf's invariant: a slot that holds no centre holds r^2 = -1
     range_group<SELF, FILL>(t, qv, g, radius, radii, out_cnt, offsets, out_idx, published[wave_in_block()], lane);
+}
+
+// k_range<true, false> with the one radius of the launch a float in device memory (the density filter of pcpx_outliers.hip, whose
+// radius an earlier kernel on the stream has left there): one uniform scalar load per wave, then the same group walk, so the same
+// bits.  A NaN radius gives r^2 = NaN: no box is needed, no point is inside, every count is 0.
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void k_range_radius_at(TreeView t, QueryView qv, u32 group_first, u32 group_end,
+                                                                         const float* __restrict__ radius_at, u32* __restrict__ out_cnt)
+{
+    __shared__ float4 published[WAVES_PER_BLOCK][32];
+    const u32 lane = threadIdx.x & 63u;
+    const u32 g = group_first + virtual_block() * WAVES_PER_BLOCK + wave_in_block();
+    if (g >= group_end) return;
+    if (lane < 32u) published[wave_in_block()][lane].w = -1.f;
+    const float radius = load_const(radius_at);
+    range_group<true, false>(t, qv, g, radius, nullptr, out_cnt, nullptr, nullptr, published[wave_in_block()], lane);
+}
+
+// The at-least form of the self count walk: keep = the sphere holds at_least (>= 1) points, by input row.  The one radius of the
+// launch is `radius`, or the float at radius_at when that is not null.
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void k_range_at_least(TreeView t, QueryView qv, u32 group_first, u32 group_end, float radius,
+                                                                        const float* __restrict__ radius_at, u32 at_least,
+                                                                        uint8_t* __restrict__ keep)
+{
+    __shared__ float4 published[WAVES_PER_BLOCK][32];
+    const u32 lane = threadIdx.x & 63u;
+    const u32 g = group_first + virtual_block() * WAVES_PER_BLOCK + wave_in_block();
+    if (g >= group_end) return;
+    if (lane < 32u) published[wave_in_block()][lane].w = -1.f;
+    if (radius_at) radius = load_const(radius_at);
+    range_group<true, false, 0, true>(t, qv, g, radius, nullptr, nullptr, nullptr, nullptr, published[wave_in_block()], lane, MomentsOut{},
+                                      FeaturesOut{}, at_least, keep);
 }
 
 // The moments form: one lane per sphere as k_range, no LDS (lane-per-range leaves); outputs by input row (self) or query row (batch)
@@ -541,6 +587,25 @@ int launch_range_count(Index& ix, const QueryView& qv, bool self, u64 group_firs
     else
         k_range<false, false><<<grid, 64 * WAVES_PER_BLOCK, 0, ix.stream>>>(ix.view(), qv, gf, ge, radius, d_radii, d_out_cnt, nullptr, nullptr);
     return check_hip(hipGetLastError(), "k_range launch", __FILE__, __LINE__);
+}
+
+int launch_range_count_self_radius_at(Index& ix, const QueryView& qv, u64 group_first, u64 group_count, const float* d_radius, u32* d_out_cnt)
+{
+    if (group_count == 0) return PCPX_OK;
+    ProfileScope prof(ix, PCPX_K_RANGE);
+    k_range_radius_at<<<grid_for_groups(group_count), 64 * WAVES_PER_BLOCK, 0, ix.stream>>>(
+        ix.view(), qv, static_cast<u32>(group_first), static_cast<u32>(group_first + group_count), d_radius, d_out_cnt);
+    return check_hip(hipGetLastError(), "k_range_radius_at launch", __FILE__, __LINE__);
+}
+
+int launch_range_at_least_self(Index& ix, const QueryView& qv, u64 group_first, u64 group_count, float radius, const float* d_radius, u32 at_least,
+                               uint8_t* d_keep)
+{
+    if (group_count == 0) return PCPX_OK;
+    ProfileScope prof(ix, PCPX_K_RANGE);
+    k_range_at_least<<<grid_for_groups(group_count), 64 * WAVES_PER_BLOCK, 0, ix.stream>>>(
+        ix.view(), qv, static_cast<u32>(group_first), static_cast<u32>(group_first + group_count), radius, d_radius, at_least, d_keep);
+    return check_hip(hipGetLastError(), "k_range_at_least launch", __FILE__, __LINE__);
 }
 
 int launch_range_fill(Index& ix, const QueryView& qv, float radius, const float* d_radii, const u64* d_offsets,

@@ -524,6 +524,89 @@ class Index:
         check(self._lib.pcpx_iss_keypoints_self_dev(self._h, float(salient_radius), float(non_max_radius), float(gamma21), float(gamma32),
                                                     int(min_neighbours), 0, *(self._dptr(d) for d in (d_keep, d_kept_rows, d_kept_count, d_saliency))))
 
+    # ---- outlier removal (include/pcpx_outliers.h) ----
+    def _outlier_result(self, kept, count, keep, want_keep, *extras):
+        out = (kept[:int(count.value)].copy(),)
+        if want_keep:
+            out += (keep.astype(bool),)
+        out += tuple(e for e in extras if e is not None)
+        return out[0] if len(out) == 1 else out
+
+    def resolution(self, k=15, eps=1e-5, want_mean_dist=False):
+        """The cloud's resolution: mean and sample standard deviation (float64, one fixed summation order: every bit depends on the
+        cloud alone) of the mean distance to the k nearest neighbours over the usable rows -- indexed, with a finite mean distance.
+        Returns (mean, std, usable)[, the mean distances float32 (n_in,), NaN outside the voxel grid]."""
+        stats = np.empty(4, np.float64)
+        d = np.empty(self.n_in, np.float32) if want_mean_dist else None
+        check(self._lib.pcpx_outliers_resolution_self(self._h, int(k), float(eps), 0, _vp(d), _vp(stats)))
+        out = (float(stats[0]), float(stats[1]), int(stats[3]))
+        return out + (d,) if want_mean_dist else out
+
+    def resolution_dev(self, d_stats, k=15, eps=1e-5, d_mean_dist=None):
+        """Device form (d_stats: 4 float64 {mean, std, NaN, usable}; d_mean_dist float32 by input row), enqueued on the index's stream
+        with no synchronisation."""
+        check(self._lib.pcpx_outliers_resolution_self(self._h, int(k), float(eps), _capi.PCPX_OUTLIERS_ON_DEVICE, self._dptr(d_mean_dist),
+                                                      self._dptr(d_stats)))
+
+    def statistical_outliers(self, k=15, std_ratio=2.0, eps=1e-5, want_keep=False, want_mean_dist=False, want_stats=False):
+        """Statistical outlier removal: keeps the usable rows whose mean distance d to their k nearest neighbours is
+        <= float32(mean + std_ratio * std), mean and std as resolution(k) gives them.
+        Returns the kept input indices, ascending (uint32)[, the keep mask bool (n_in,)][, d float32 (n_in,)][, stats float64 (4,):
+        mean, std, the cut, the usable rows]."""
+        keep = np.empty(self.n_in, np.uint8)
+        kept = np.empty(self.n_in, np.uint32)
+        d = np.empty(self.n_in, np.float32) if want_mean_dist else None
+        stats = np.empty(4, np.float64) if want_stats else None
+        count = C.c_uint64(0)
+        check(self._lib.pcpx_outliers_statistical_self(self._h, int(k), float(eps), float(std_ratio), 0, _vp(keep), _vp(kept), C.byref(count),
+                                                       _vp(d), _vp(stats)))
+        return self._outlier_result(kept, count, keep, want_keep, d, stats)
+
+    def statistical_outliers_dev(self, d_keep, k=15, std_ratio=2.0, eps=1e-5, d_kept_rows=None, d_kept_count=None, d_mean_dist=None,
+                                 d_stats=None):
+        """Device form (torch tensors or pointers to device arrays: keep uint8 by input row, kept_rows uint32 with room for n_in
+        entries, d_kept_count one uint64, d_mean_dist float32 by input row, d_stats 4 float64), enqueued on the index's stream with
+        no synchronisation."""
+        check(self._lib.pcpx_outliers_statistical_self(self._h, int(k), float(eps), float(std_ratio), _capi.PCPX_OUTLIERS_ON_DEVICE,
+                                                       *(self._dptr(d) for d in (d_keep, d_kept_rows, d_kept_count, d_mean_dist, d_stats))))
+
+    def radius_outliers(self, radius, min_neighbours=5, want_keep=False, want_counts=False):
+        """Radius outlier removal: keeps the indexed points whose sphere (the rule of range_count_self, the point itself included)
+        holds at least max(min_neighbours, 1) points.  Without the counts the walk stops a point at the bound.
+        Returns the kept input indices, ascending (uint32)[, the keep mask bool (n_in,)][, the counts uint32 (n_in,)]."""
+        keep = np.empty(self.n_in, np.uint8)
+        kept = np.empty(self.n_in, np.uint32)
+        cnt = np.empty(self.n_in, np.uint32) if want_counts else None
+        count = C.c_uint64(0)
+        check(self._lib.pcpx_outliers_radius_self(self._h, float(radius), int(min_neighbours), 0, _vp(keep), _vp(kept), C.byref(count), _vp(cnt)))
+        return self._outlier_result(kept, count, keep, want_keep, cnt)
+
+    def radius_outliers_dev(self, radius, d_keep, min_neighbours=5, d_kept_rows=None, d_kept_count=None, d_count=None):
+        """Device form (as statistical_outliers_dev; d_count uint32 by input row), enqueued on the index's stream."""
+        check(self._lib.pcpx_outliers_radius_self(self._h, float(radius), int(min_neighbours), _capi.PCPX_OUTLIERS_ON_DEVICE,
+                                                  *(self._dptr(d) for d in (d_keep, d_kept_rows, d_kept_count, d_count))))
+
+    def density_outliers(self, k=15, radius_scale=1.0, min_neighbours=5, eps=1e-5, want_keep=False, want_counts=False, want_stats=False):
+        """The reference's filter_point_cloud_noise_by_density in one call: radius_outliers at float32(radius_scale * mean) with the
+        mean of resolution(k); the radius stays on the device.
+        Returns the kept input indices, ascending (uint32)[, the keep mask][, the counts][, stats float64 (4,): mean, std, the radius,
+        the usable rows]."""
+        keep = np.empty(self.n_in, np.uint8)
+        kept = np.empty(self.n_in, np.uint32)
+        cnt = np.empty(self.n_in, np.uint32) if want_counts else None
+        stats = np.empty(4, np.float64) if want_stats else None
+        count = C.c_uint64(0)
+        check(self._lib.pcpx_outliers_density_self(self._h, int(k), float(eps), float(radius_scale), int(min_neighbours), 0, _vp(keep), _vp(kept),
+                                                   C.byref(count), _vp(cnt), _vp(stats)))
+        return self._outlier_result(kept, count, keep, want_keep, cnt, stats)
+
+    def density_outliers_dev(self, d_keep, k=15, radius_scale=1.0, min_neighbours=5, eps=1e-5, d_kept_rows=None, d_kept_count=None, d_count=None,
+                             d_stats=None):
+        """Device form (as radius_outliers_dev; d_stats 4 float64), enqueued on the index's stream."""
+        check(self._lib.pcpx_outliers_density_self(self._h, int(k), float(eps), float(radius_scale), int(min_neighbours),
+                                                   _capi.PCPX_OUTLIERS_ON_DEVICE,
+                                                   *(self._dptr(d) for d in (d_keep, d_kept_rows, d_kept_count, d_count, d_stats))))
+
     # ---- descriptors (include/pcpx_descriptors.h) ----
     def fpfh(self, normals, radius, rows=None, want_spfh=False):
         """Fast Point Feature Histograms (Rusu et al. 2009) over `radius` from `normals` (n_in x 3, float32, used as given): 33 floats
