@@ -128,6 +128,10 @@ int pcpx_device_count(int* out_count);
 /* ---- index construction: replaces the octree / kd-tree constructors ---------------------- */
 int pcpx_index_create(const float* xyz, uint64_t n, const pcpx_build_params* params, int device,
                       pcpx_index** out);
+/* The *_dev builds read a device cloud in stream order: their kernels are enqueued on `stream`, which becomes the handle's.  Unlike
+ * the general rule they wait for `stream` (a rebuild: the handle's) once, at the end of the build, for the one read-back of the
+ * counts and the box that pcpx_index_size / pcpx_index_bbox then answer from the host (an explicit grid is uploaded from the
+ * caller's params with a wait of its own at the start; growing the handle's arrays waits too). */
 int pcpx_index_create_dev(const float* d_xyz, uint64_t n, const pcpx_build_params* params, int device,
                           void* stream, pcpx_index** out);
 /* Re-index a new cloud in place, reusing device buffers (BASELINE config 5: rebuild per iteration). */
@@ -146,6 +150,8 @@ int pcpx_index_shard_info(pcpx_index* idx, uint64_t out[8]);
 /* pcp::bounding_box over a host slice (axis_aligned_bounding_box.hpp:214-251): the per-rank step
  * before the bounding-box all-gather of the multi-GPU path. */
 int pcpx_bounding_box(const float* xyz, uint64_t n, int device, float out6[6]);
+/* The same over a device slice, d_out6 six device floats.  Fully enqueued on `stream`: no read-back and no synchronisation; its
+ * 256 bytes of scratch stay taken from the device's pool until the stream has passed the call (pcpx_match.h). */
 int pcpx_bounding_box_dev(const float* d_xyz, uint64_t n, int device, void* stream, float* d_out6);
 
 /* ---- k nearest neighbours: replaces nearest_neighbours ----------------------------------- */
@@ -321,7 +327,8 @@ int pcpx_bilateral_filter_normals_dev(const float* d_xyz, const float* d_normals
  * caller names the seed points (sample[i] < n, n_samples <= n), everything after that is the reference's:
  * v_j over the cloud (uniform != 0, :29-65), then per iteration a tree over x, w_i (:67-105), and
  * x' = median of the cloud around x (:107-170) + mu-weighted repulsion among x (:172-229), radius h.
- * out_xyz is n_samples x 3 (iterations == 0: the seed points). */
+ * out_xyz is n_samples x 3 (iterations == 0: the seed points).  pcpx_wlop_dev takes device arrays, runs on `stream` (NULL = the
+ * legacy default stream) and returns after the work has completed. */
 int pcpx_wlop(const float* xyz, uint64_t n, const uint64_t* sample, uint64_t n_samples, double mu, double h,
               uint64_t iterations, int uniform, int device, float* out_xyz);
 int pcpx_wlop_dev(const float* d_xyz, uint64_t n, const uint64_t* d_sample, uint64_t n_samples, double mu, double h,
@@ -540,7 +547,9 @@ int pcpx_tangent_plane_sdf_dev(pcpx_index* idx, const float* d_centroids, const 
  * oriented by the device orientation pass, the grid regular_grid_containing(box of the index, dims), the field above and
  * surface nets at `isovalue`; only counts cross to the host.  Outputs as pcpx_surface_nets_dev (a short buffer: the whole
  * pipeline runs again on the second call); opt_out_centroids / opt_out_normals (n x 3, input order) receive the oriented
- * planes, opt_out_grid the grid.  PCPX_ERR_UNSUPPORTED if points were dropped by an explicit voxel grid. */
+ * planes, opt_out_grid the grid.  PCPX_ERR_UNSUPPORTED if points were dropped by an explicit voxel grid.  The _dev form takes
+ * device arrays and waits for the handle's stream more than once: the orientation pass, the field and surface nets each wait as
+ * their own entry points do, and the counts are on the host when it returns. */
 int pcpx_reconstruct_surface(pcpx_index* idx, uint32_t k, float eps, const uint64_t dims[3], float isovalue, float* out_xyz,
                              uint64_t vertex_capacity, uint32_t* out_tri, uint64_t triangle_capacity, uint64_t* out_nvertices,
                              uint64_t* out_ntriangles, float* opt_out_centroids, float* opt_out_normals, pcpx_grid3d* opt_out_grid);

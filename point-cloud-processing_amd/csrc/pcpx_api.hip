@@ -377,17 +377,10 @@ int pcpx_index_synchronize(pcpx_index* h)
 
 int pcpx_bounding_box_dev(const float* d_xyz, uint64_t n, int device, void* stream, float* d_out6)
 {
-    return on_shared(device, "pcpx_bounding_box_dev", [&](DeviceShared& shared) -> int {
-    int st;
     if (!d_out6 || (n > 0 && !d_xyz)) return PCPX_ERR_INVALID;
-    // d_out6 must have room for the 6 floats; the encoded scratch is a temporary
-    DevBuf enc(shared.pool);
-    if ((st = enc.alloc(64 * sizeof(u32))) != PCPX_OK) return st;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    st = device_bbox(d_xyz, n, s, enc.as<u32>(), d_out6, false);
-    if (st != PCPX_OK) return st;
-    PCPX_HIP(hipStreamSynchronize(s));  // enc goes back to the pool on return
-    return PCPX_OK;
+    // d_out6 must have room for the 6 floats; the encoded scratch is a lease: it stays taken until the stream has passed the call
+    return on_leased(device, "pcpx_bounding_box_dev", stream, 64 * sizeof(u32), [&](char* base, hipStream_t s) -> int {
+    return device_bbox(d_xyz, n, s, reinterpret_cast<u32*>(base), d_out6, false);
     });
 }
 int pcpx_bounding_box(const float* xyz, uint64_t n, int device, float out6[6])

@@ -111,7 +111,7 @@ def _knn_slice(c, k, stride):
     idx, cnt, d2 = c.out(c.n_in * stride, "u32"), c.out(c.n_in, "u32"), c.out(c.n_in * stride, "f32")
     c.ready()
     c.ix.knn_self_strided_dev(k, EPS, stride, idx.data_ptr(), cnt.data_ptr(), d2.data_ptr(), first, count)
-    c.ix.synchronize()
+    c.drain()
     return {"idx": c.down(idx, c.n_in * stride, stride), "cnt": c.down(cnt, c.n_in), "d2": c.down(d2, c.n_in * stride, stride)}
 
 
@@ -120,7 +120,7 @@ def _knn_batch(c, k):
     dq, idx, cnt, d2 = c.up(q), c.out(len(q) * k, "u32"), c.out(len(q), "u32"), c.out(len(q) * k, "f32")
     c.ready()
     c.ix.knn_batch_dev(dq.data_ptr(), len(q), k, EPS, idx.data_ptr(), cnt.data_ptr(), d2.data_ptr())
-    c.ix.synchronize()
+    c.drain()
     return {"idx": c.down(idx, len(q) * k, k), "cnt": c.down(cnt, len(q)), "d2": c.down(d2, len(q) * k, k)}
 
 
@@ -129,7 +129,7 @@ def _normals_strided(c, k, stride, sliced):
     nrm, idx, cnt = c.out(c.n_in * 3, "f32"), c.out(c.n_in * stride, "u32"), c.out(c.n_in, "u32")
     c.ready()
     c.ix.normals_knn_self_strided_dev(k, EPS, stride, nrm.data_ptr(), idx.data_ptr(), cnt.data_ptr(), first, count)
-    c.ix.synchronize()
+    c.drain()
     return {"normals": c.down(nrm, c.n_in * 3, 3), "idx": c.down(idx, c.n_in * stride, stride), "cnt": c.down(cnt, c.n_in)}
 
 
@@ -142,7 +142,7 @@ def _group_costs(c):
     ev = c.out(4 * ns.value, "u32")
     c.ready()
     assert lib.pcpx_knn_group_costs_dev(c.ix._h, 8, EPS, stride, ev.data_ptr(), ns.value, C.byref(ns)) == 0
-    c.ix.synchronize()
+    c.drain()
     return {"events": c.down(ev, 4 * ns.value, 4)}
 
 
@@ -152,7 +152,7 @@ def _propagate(c):
     nrm = c.ix.normals_knn_self(k, EPS)
     dx, di, dc, dn = c.up(c.I["points"]), c.up(idx), c.up(cnt), c.up(nrm, "normals, updated in place")
     c.ready()
-    reached, levels = c.pkg.propagate_normal_orientations_dev(dx.data_ptr(), c.n_in, di.data_ptr(), dc.data_ptr(), k, dn.data_ptr())
+    reached, levels = c.pkg.propagate_normal_orientations_dev(dx.data_ptr(), c.n_in, di.data_ptr(), dc.data_ptr(), k, dn.data_ptr(), stream=c.stream)
     c.ready()
     return {"normals": c.down(dn, c.n_in * 3, 3), "words": np.array([reached, levels], np.uint64)}
 
@@ -164,7 +164,7 @@ def _count(c, sliced):
     c.ready()
     c.ix.range_count_self_dev(c.r, cnt.data_ptr(), first, count)
     c.ix.range_count_self_curve_order_dev(c.r, at.data_ptr(), first, count)
-    c.ix.synchronize()
+    c.drain()
     return {"cnt": c.down(cnt, c.n_in), "cnt_by_position": c.down(at, c.n)}
 
 
@@ -180,7 +180,7 @@ def _sphere_rows(c, call, widths, sliced, first_count=slice_of):
     outs = {name: c.out(c.n_in * w, kind) for name, (w, kind) in widths.items()}
     c.ready()
     call(c, [t.data_ptr() for t in outs.values()], first, count)
-    c.ix.synchronize()
+    c.drain()
     return {name: c.down(outs[name], c.n_in * w, w) for name, (w, _kind) in widths.items()}
 
 
@@ -214,7 +214,7 @@ def _segment(c, curvature):
     c.ready()
     c.ix.segment_dev(nrm.data_ptr(), c.r, lab.data_ptr(), min_cos=0.5, d_curvature=ptr(cur), max_curvature=0.5, min_size=3,
                      d_smooth=smooth.data_ptr(), d_segment_count=count.data_ptr())
-    c.ix.synchronize()
+    c.drain()
     return {"labels": c.down(lab, c.n_in), "smooth": c.down(smooth, c.n_in), "count": c.down(count, 1)}
 
 
@@ -222,7 +222,7 @@ def _subsample(c):
     keep, owner, kept, count = c.out(c.n_in, "u8"), c.out(c.n_in, "u32"), c.out(c.n_in, "u32"), c.out(1, "u64")
     c.ready()
     c.ix.subsample_dev(c.r, keep.data_ptr(), HH.SUBSAMPLE_SEED, owner.data_ptr(), kept.data_ptr(), count.data_ptr())
-    c.ix.synchronize()
+    c.drain()
     return {"keep": c.down(keep, c.n_in), "owner": c.down(owner, c.n_in), "kept": c.down(kept, c.n_in), "count": c.down(count, 1)}
 
 
@@ -230,7 +230,7 @@ def _local_maxima(c):
     score, keep, kept, count = c.up(c.I["score"]), c.out(c.n_in, "u8"), c.out(c.n_in, "u32"), c.out(1, "u64")
     c.ready()
     c.ix.local_maxima_dev(score, c.r, keep, min_score=0.25, min_neighbours=2, d_kept_rows=kept, d_kept_count=count)
-    c.ix.synchronize()
+    c.drain()
     return {"keep": c.down(keep, c.n_in), "kept": c.down(kept, c.n_in), "count": c.down(count, 1)}
 
 
@@ -238,7 +238,7 @@ def _iss(c):
     keep, kept, count, sal = c.out(c.n_in, "u8"), c.out(c.n_in, "u32"), c.out(1, "u64"), c.out(c.n_in, "f32")
     c.ready()
     c.ix.iss_keypoints_dev(c.r, 1.5 * c.r, keep, min_neighbours=2, d_kept_rows=kept, d_kept_count=count, d_saliency=sal)
-    c.ix.synchronize()
+    c.drain()
     return {"keep": c.down(keep, c.n_in), "kept": c.down(kept, c.n_in), "count": c.down(count, 1), "saliency": c.down(sal, c.n_in)}
 
 
@@ -249,7 +249,7 @@ def _fpfh(c, subset):
     fpfh, spfh, pairs = c.out(m * 33, "f32"), c.out(c.n_in * 33, "f32"), c.out(c.n_in, "u32")
     c.ready()
     c.ix.fpfh_dev(nrm, c.r, fpfh, d_rows=drows, m=m if subset else 0, d_spfh=spfh, d_pairs=pairs)
-    c.ix.synchronize()
+    c.drain()
     return {"fpfh": c.down(fpfh, m * 33, 33), "spfh": c.down(spfh, c.n_in * 33, 33), "pairs": c.down(pairs, c.n_in)}
 
 
@@ -259,7 +259,7 @@ def _nearest(c):
     src, pose, partner, d2 = c.up(s), c.up(HH.POSE.reshape(16)), c.out(len(s), "u32"), c.out(len(s), "f32")
     c.ready()
     c.ix.nearest_posed_dev(src, len(s), 2.0 * c.r, partner, d_pose=pose, d_d2=d2)
-    c.ix.synchronize()
+    c.drain()
     return {"partner": c.down(partner, len(s)), "d2": c.down(d2, len(s))}
 
 
@@ -270,7 +270,7 @@ def _icp(c, plane):
     c.ready()
     c.ix.icp_dev(src, m, 2.0 * c.r, xf, max_iterations=it, d_normals=nrm, d_status=words[0], d_iterations=words[1], d_last_count=words[2],
                  d_count=count, d_rms=rms, d_partner=partner)
-    c.ix.synchronize()
+    c.drain()
     return {"transform": c.down(xf, 16), "words": np.concatenate([c.down(w, 1) for w in words]), "count": c.down(count, it), "rms": c.down(rms, it),
             "partner": c.down(partner, m)}
 
@@ -292,7 +292,7 @@ def _sdf(c):
     dc, dn, field = c.up(cen), c.up(nrm), c.out(corners, "f32")
     c.ready()
     S.check(S._capi.load().pcpx_tangent_plane_sdf_dev(c.ix._h, dc.data_ptr(), dn.data_ptr(), C.byref(g), EPS, field.data_ptr()))
-    c.ix.synchronize()
+    c.drain()
     return {"field": c.down(field, corners)}
 
 
@@ -307,7 +307,7 @@ def _reconstruct(c):
     c.ready()
     S.check(S._capi.load().pcpx_reconstruct_surface_dev(c.ix._h, HH.RECONSTRUCT_K, EPS, d.ctypes.data_as(S._capi.u64p), 0.0, dv.data_ptr(), V, dt.data_ptr(),
                                                         T, C.byref(nv), C.byref(nt), dc.data_ptr(), dn.data_ptr(), None))
-    c.ix.synchronize()
+    c.drain()
     return {"counts": np.array([nv.value, nt.value], np.uint64), "vertices": c.down(dv, V * 3, 3), "triangles": c.down(dt, T * 3, 3),
             "centroids": c.down(dc, c.n_in * 3, 3), "normals": c.down(dn, c.n_in * 3, 3)}
 
@@ -337,12 +337,12 @@ def _nets(c, hint, timed):
     def call(v, V, t, T):
         mesh = (ptr(v), V, ptr(t), T, C.byref(nv), C.byref(nt))
         if hint and timed:
-            return lib.pcpx_surface_nets_hint_timed_dev(df.data_ptr(), C.byref(g), 0.0, hp, 32768, 0, None, *mesh, C.byref(seed), ms, C.byref(rounds))
+            return lib.pcpx_surface_nets_hint_timed_dev(df.data_ptr(), C.byref(g), 0.0, hp, 32768, 0, c.stream, *mesh, C.byref(seed), ms, C.byref(rounds))
         if hint:
-            return lib.pcpx_surface_nets_hint_dev(df.data_ptr(), C.byref(g), 0.0, hp, 32768, 0, None, *mesh, C.byref(seed))
+            return lib.pcpx_surface_nets_hint_dev(df.data_ptr(), C.byref(g), 0.0, hp, 32768, 0, c.stream, *mesh, C.byref(seed))
         if timed:
-            return lib.pcpx_surface_nets_timed_dev(df.data_ptr(), C.byref(g), 0.0, 0, None, *mesh, ms)
-        return lib.pcpx_surface_nets_dev(df.data_ptr(), C.byref(g), 0.0, 0, None, *mesh)
+            return lib.pcpx_surface_nets_timed_dev(df.data_ptr(), C.byref(g), 0.0, 0, c.stream, *mesh, ms)
+        return lib.pcpx_surface_nets_dev(df.data_ptr(), C.byref(g), 0.0, 0, c.stream, *mesh)
     c.ready()
     assert call(None, 0, None, 0) == S._capi.PCPX_ERR_CAPACITY  # (the sizes; then buffers of exactly those)
     V, T = nv.value, nt.value
@@ -363,7 +363,7 @@ def _bilateral(c, normals_mode):
     f = lib.pcpx_bilateral_filter_normals_dev if normals_mode else lib.pcpx_bilateral_filter_points_dev
     c.ready()
     c.pkg.surface.check(f(dp.data_ptr(), dn.data_ptr(), len(pts), C.c_double(HH.BILATERAL["sigmaf"]), C.c_double(HH.BILATERAL["sigmag"]), HH.BILATERAL["K"],
-                          0, None, out.data_ptr()))
+                          0, c.stream, out.data_ptr()))
     c.ready()
     return {"out": c.down(out, len(pts) * 3, 3)}
 
@@ -374,7 +374,7 @@ def _wlop(c):
     dp, ds, out = c.up(pts), c.up(sample), c.out(len(sample) * 3, "f32")
     c.ready()
     c.pkg.surface.check(lib.pcpx_wlop_dev(dp.data_ptr(), len(pts), ds.data_ptr(), len(sample), C.c_double(HH.WLOP["mu"]), C.c_double(HH.WLOP["h"]),
-                                          HH.WLOP["k"], 1, 0, None, out.data_ptr()))
+                                          HH.WLOP["k"], 1, 0, c.stream, out.data_ptr()))
     c.ready()
     return {"out": c.down(out, len(sample) * 3, 3)}
 
@@ -387,12 +387,12 @@ def _hierarchy(c):
     dp = c.up(pts)
     count = C.c_uint64(0)
     c.ready()
-    assert lib.pcpx_hierarchy_simplification_dev(dp.data_ptr(), len(pts), C.byref(prm), 0, None, None, None, 0, C.byref(count)) == S._capi.PCPX_ERR_CAPACITY
+    assert lib.pcpx_hierarchy_simplification_dev(dp.data_ptr(), len(pts), C.byref(prm), 0, c.stream, None, None, 0, C.byref(count)) == S._capi.PCPX_ERR_CAPACITY
     K = count.value
     assert 0 < K < len(pts)
     out, idx = c.out(K * 3, "f32"), c.out(K, "u32")
     c.ready()
-    S.check(lib.pcpx_hierarchy_simplification_dev(dp.data_ptr(), len(pts), C.byref(prm), 0, None, out.data_ptr(), idx.data_ptr(), K, C.byref(count)))
+    S.check(lib.pcpx_hierarchy_simplification_dev(dp.data_ptr(), len(pts), C.byref(prm), 0, c.stream, out.data_ptr(), idx.data_ptr(), K, C.byref(count)))
     c.ready()
     return {"count": np.array([count.value], np.uint64), "points": c.down(out, K * 3, 3), "idx": c.down(idx, K)}
 
@@ -403,7 +403,7 @@ def _match_nearest(c):
     ds, dt = c.up(src), c.up(tgt)
     idx, d2, idx2, d22 = c.out(m, "u32"), c.out(m, "f32"), c.out(m, "u32"), c.out(m, "f32")
     c.ready()
-    c.pkg.match_nearest_dev(ds, m, dt, len(tgt), HH.MATCH_DIMS, idx, d2, idx2, d22)
+    c.pkg.match_nearest_dev(ds, m, dt, len(tgt), HH.MATCH_DIMS, idx, d2, idx2, d22, stream=c.stream)
     c.ready()
     return {"idx": c.down(idx, m), "d2": c.down(d2, m), "second_idx": c.down(idx2, m), "second_d2": c.down(d22, m)}
 
@@ -414,7 +414,7 @@ def _match_pairs(c):
     ds, dt = c.up(src), c.up(tgt)
     pairs, d2, count = c.out(2 * m, "u32"), c.out(m, "f32"), c.out(1, "u64")  # (room for m pairs: the call takes no capacity)
     c.ready()
-    c.pkg.match_correspondences_dev(ds, m, dt, len(tgt), HH.MATCH_DIMS, pairs, d2, count, 1.0, True)
+    c.pkg.match_correspondences_dev(ds, m, dt, len(tgt), HH.MATCH_DIMS, pairs, d2, count, 1.0, True, stream=c.stream)
     c.ready()
     got = {"pairs": c.down(pairs, 2 * m, 2), "d2": c.down(d2, m), "count": c.down(count, 1)}
     assert 0 < int(got["count"][0]) < m  # (some pairs, and some caller's entries behind them)
@@ -430,7 +430,7 @@ def _ransac_rigid(c):
     inl, xf, refit = c.out(n, "u32"), c.out(16, "f64"), c.out(16, "f64")
     c.ready()
     c.pkg.ransac_rigid_dev(dP, len(P), dQ, len(Q), dpairs, n, HH.RANSAC["T"], tau, found, d_hypothesis=h, d_score=score, d_inliers=inl, d_inlier_count=ninl,
-                           d_transform=xf, d_refit=refit, seed=TR.SEED, edge_similarity=HH.RANSAC["s"])
+                           d_transform=xf, d_refit=refit, seed=TR.SEED, edge_similarity=HH.RANSAC["s"], stream=c.stream)
     c.ready()
     return {"words": np.concatenate([c.down(found, 1), c.down(h, 1), c.down(score, 1)]), "ninl": c.down(ninl, 1), "inliers": c.down(inl, n),
             "xf": c.down(xf, 16), "refit": c.down(refit, 16)}
@@ -441,7 +441,7 @@ def _rigid_fit(c):
     pairs = np.ascontiguousarray(S["pairs"], np.uint32).reshape(-1, 2)
     dP, dQ, dpairs, xf, rms = c.up(S["P"]), c.up(S["Q"]), c.up(pairs), c.out(16, "f64"), c.out(1, "f64")
     c.ready()
-    c.pkg.rigid_fit_dev(dP, len(S["P"]), dQ, len(S["Q"]), dpairs, len(pairs), xf, d_rms=rms)
+    c.pkg.rigid_fit_dev(dP, len(S["P"]), dQ, len(S["Q"]), dpairs, len(pairs), xf, d_rms=rms, stream=c.stream)
     c.ready()
     return {"transform": c.down(xf, 16), "rms": c.down(rms, 1)}
 
@@ -456,7 +456,7 @@ def _plane_ransac(c):
     prm = c.pkg.planes.plane_params(HH.PLANE["T"], tau, TP.SEED, True, TP.COSN, TP.UP, TP.COSA)  # (both gates: the normals are read too)
     c.ready()
     c.pkg.ransac_plane_dev(dP, len(P), prm, found, d_normals=dN, d_rows=drows, rows_capacity=n, d_hypothesis=h, d_score=score, d_inliers=inl,
-                           d_inlier_count=ninl, d_plane=plane, d_refit=refit)
+                           d_inlier_count=ninl, d_plane=plane, d_refit=refit, stream=c.stream)
     c.ready()
     return {"words": np.concatenate([c.down(found, 1), c.down(h, 1), c.down(score, 1)]), "ninl": c.down(ninl, 1), "inliers": c.down(inl, n),
             "plane": c.down(plane, 4), "refit": c.down(refit, 4)}
@@ -467,7 +467,7 @@ def _plane_fit(c):
     rows = np.arange(len(P) - 1, -1, -3).astype(np.uint32)
     dP, drows, plane, rms = c.up(P), c.up(rows), c.out(4, "f64"), c.out(1, "f64")
     c.ready()
-    c.pkg.plane_fit_dev(dP, len(P), plane, d_rows=drows, rows_capacity=len(rows), d_rms=rms)
+    c.pkg.plane_fit_dev(dP, len(P), plane, d_rows=drows, rows_capacity=len(rows), d_rms=rms, stream=c.stream)
     c.ready()
     return {"plane": c.down(plane, 4), "rms": c.down(rms, 1)}
 
@@ -480,7 +480,7 @@ def _extract_planes(c):
     dP = c.up(P)
     labels, count, planes, refits, scores = c.out(len(P), "u32"), c.out(1, "u32"), c.out(4 * M, "f64"), c.out(4 * M, "f64"), c.out(M, "u32")
     c.ready()
-    c.pkg.extract_planes_dev(dP, len(P), prm, labels, count, d_planes=planes, d_refits=refits, d_scores=scores)
+    c.pkg.extract_planes_dev(dP, len(P), prm, labels, count, d_planes=planes, d_refits=refits, d_scores=scores, stream=c.stream)
     c.ready()
     return {"labels": c.down(labels, len(P)), "count": c.down(count, 1), "planes": c.down(planes, 4 * M, 4), "refits": c.down(refits, 4 * M, 4),
             "scores": c.down(scores, M)}
@@ -494,14 +494,14 @@ def _voxel(c):
     dP, dQ = c.up(s["P"]), c.up(s["attrs"]) if A else None
     count, dropped, origin, owner = c.out(1, "u64"), c.out(1, "u64"), c.out(3, "f32"), c.out(n, "u32")
     c.ready()
-    c.pkg.voxel_grid_dev(dP, n, prm, 0, count, d_attrs=dQ)  # (no room: the count alone)
+    c.pkg.voxel_grid_dev(dP, n, prm, 0, count, d_attrs=dQ, stream=c.stream)  # (no room: the count alone)
     c.ready()
     V = int(c.down(count, 1)[0])
     assert 0 < V < n
     xyz, mean, counts, keys, rows = c.out(V * 3, "f32"), c.out(V * A, "f32") if A else None, c.out(V, "u32"), c.out(V, "u64"), c.out(V, "u32")
     c.ready()
     c.pkg.voxel_grid_dev(dP, n, prm, V, count, d_attrs=dQ, d_xyz=xyz, d_mean=mean, d_counts=counts, d_keys=keys, d_rows=rows, d_owner=owner, d_dropped=dropped,
-                         d_origin=origin)
+                         d_origin=origin, stream=c.stream)
     c.ready()
     got = {"count": c.down(count, 1), "dropped": c.down(dropped, 1), "origin": c.down(origin, 3), "owner": c.down(owner, n), "xyz": c.down(xyz, V * 3, 3),
            "counts": c.down(counts, V), "keys": c.down(keys, V), "rows": c.down(rows, V)}
@@ -515,7 +515,7 @@ def _bbox(c):
     pts = HH.inputs("c1300")["points"]
     dp, box = c.up(pts), c.out(6, "f32")
     c.ready()
-    c.pkg.surface.check(lib.pcpx_bounding_box_dev(dp.data_ptr(), len(pts), 0, None, box.data_ptr()))
+    c.pkg.surface.check(lib.pcpx_bounding_box_dev(dp.data_ptr(), len(pts), 0, c.stream, box.data_ptr()))
     c.ready()
     return {"box": c.down(box, 6)}
 
@@ -526,7 +526,7 @@ def _builds(c):
     a, b = HH.inputs("c1300")["points"], HH.inputs("c5000g")["points"]
     da, db = c.up(a), c.up(b)
     c.ready()
-    ix = c.pkg.Index.from_device(da.data_ptr(), len(a))
+    ix = c.pkg.Index.from_device(da.data_ptr(), len(a), stream=c.stream)
     try:
         out["create_idx"], out["create_cnt"], out["create_d2"] = ix.knn_self(8, EPS, want_d2=True)
         out["create_box"] = np.asarray(ix.bbox(), F)

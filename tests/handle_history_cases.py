@@ -156,6 +156,7 @@ def rebuild(ix, cloud):
 
 class Ctx:
     """what a row gets: the package, a handle and its cloud's inputs, and the device arrays of a _dev call"""
+    stream = None  # what a row passes to a call that takes a stream (tests/stream_order.py: the stream it holds)
 
     def __init__(self, pkg, ix, cloud):
         self.pkg, self.ix, self.cloud, self.I = pkg, ix, cloud, inputs(cloud)
@@ -183,6 +184,10 @@ class Ctx:
     def ready(self):
         self.torch().cuda.synchronize()  # (the fills are on torch's stream, a handle's call on its own)
 
+    def drain(self):
+        """after the calls on the handle: its stream is drained before an output is looked at"""
+        self.ix.synchronize()
+
     def down(self, d, length=None, width=1):
         """after the handle's stream is drained: the array on the host, unsigned, cut to `length` entries, `width` to a row"""
         a = d.cpu().numpy()
@@ -201,7 +206,7 @@ def _knn_dev(c, k, stride=0):
         c.ix.knn_self_strided_dev(k, EPS, stride, idx.data_ptr(), cnt.data_ptr(), d2.data_ptr())
     else:
         c.ix.knn_self_dev(k, EPS, idx.data_ptr(), cnt.data_ptr(), d2.data_ptr())
-    c.ix.synchronize()
+    c.drain()
     return {"idx": c.down(idx, c.n_in * w, w), "cnt": c.down(cnt, c.n_in), "d2": c.down(d2, c.n_in * w, w)}
 
 
@@ -211,7 +216,7 @@ def _knn_curve(c, k):
     c.ready()
     c.ix.knn_self_curve_order_dev(k, EPS, idx.data_ptr(), cnt.data_ptr(), d2.data_ptr(), nrm.data_ptr())
     c.ix.perm_dev(perm.data_ptr(), pos.data_ptr())
-    c.ix.synchronize()
+    c.drain()
     return {"idx": c.down(idx, c.n * k, k), "cnt": c.down(cnt, c.n), "d2": c.down(d2, c.n * k, k), "normals": c.down(nrm, c.n * 3, 3),
             "perm": c.down(perm, c.n), "position_of": c.down(pos, c.n_in)}
 
@@ -229,7 +234,7 @@ def _count_dev(c):
     c.ix.range_count_self_dev(c.r, cnt.data_ptr())
     c.ix.range_count_self_curve_order_dev(c.r, pos.data_ptr())
     c.ix.perm_dev(perm.data_ptr())
-    c.ix.synchronize()
+    c.drain()
     # (input order: the rows of the points outside the grid are the caller's, here FILL)
     return {"cnt": c.down(cnt, c.n_in), "cnt_by_position": c.down(pos, c.n), "perm": c.down(perm, c.n)}
 
@@ -241,7 +246,7 @@ def _lists_dev(c):
     idx = c.out(total, "u32")
     c.ready()
     assert c.ix.range_lists_self_dev(c.r, off.data_ptr(), idx.data_ptr(), total) == total
-    c.ix.synchronize()
+    c.drain()
     return {"offsets": c.down(off, c.n_in + 1), "idx": c.down(idx, total)}
 
 
@@ -260,7 +265,7 @@ def _normals_dev(c, k, gather):
     if gather:
         c.ix.debug_set("gather_outputs", 1)
     c.ix.normals_knn_self_dev(k, EPS, nrm.data_ptr(), idx.data_ptr(), cnt.data_ptr())
-    c.ix.synchronize()
+    c.drain()
     if gather:
         c.ix.debug_set("gather_outputs", 0)
     return {"normals": c.down(nrm, c.n_in * 3, 3), "idx": c.down(idx, c.n_in * k, k), "cnt": c.down(cnt, c.n_in)}
@@ -270,7 +275,7 @@ def _neighbourhoods_dev(c, k):
     nrm, cen, md = c.out(c.n_in * 3, "f32"), c.out(c.n_in * 3, "f32"), c.out(c.n_in, "f32")
     c.ready()
     c.ix.neighbourhoods_self_dev(k, EPS, nrm.data_ptr(), cen.data_ptr(), md.data_ptr())
-    c.ix.synchronize()
+    c.drain()
     return {"normals": c.down(nrm, c.n_in * 3, 3), "centroids": c.down(cen, c.n_in * 3, 3), "mean_dist": c.down(md, c.n_in)}
 
 
@@ -299,7 +304,7 @@ def _reconstruct_dev(c):
     c.ready()
     S.check(S._capi.load().pcpx_reconstruct_surface_dev(c.ix._h, RECONSTRUCT_K, EPS, d.ctypes.data_as(S._capi.u64p), 0.0, C.c_void_p(dv.data_ptr()), V,
                                                         C.c_void_p(dt.data_ptr()), T, C.byref(nv), C.byref(nt), None, None, None))
-    c.ix.synchronize()
+    c.drain()
     return {"counts": np.array([nv.value, nt.value], np.uint64), "vertices": c.down(dv, V * 3, 3), "triangles": c.down(dt, T * 3, 3),
             "host_vertices": first["vertices"], "host_triangles": first["triangles"], "centroids": first["centroids"], "normals": first["normals"]}
 
@@ -326,7 +331,7 @@ def _cluster_dev(c, min_pts, compact):
     lab, core, counts, count = c.out(c.n_in, "u32"), c.out(c.n_in, "u8"), c.out(c.n_in, "u32"), c.out(1, "u64")
     c.ready()
     c.ix.cluster_dev(c.r, lab.data_ptr(), min_pts, compact, core.data_ptr(), counts.data_ptr(), count.data_ptr())
-    c.ix.synchronize()
+    c.drain()
     return {"labels": c.down(lab, c.n_in), "count": c.down(count, 1), "core": c.down(core, c.n_in), "counts": c.down(counts, c.n_in)}
 
 
@@ -395,7 +400,7 @@ def _icp(c, plane):
     c.ready()
     c.ix.icp_dev(src, m, 2.0 * c.r, xf, max_iterations=ICP_ITERATIONS, d_normals=nrm, d_status=words[0], d_iterations=words[1], d_last_count=words[2],
                  d_count=count, d_rms=rms, d_partner=partner)
-    c.ix.synchronize()
+    c.drain()
     out.update({"dev_transform": c.down(xf, 16), "dev_words": np.concatenate([c.down(w, 1) for w in words]), "dev_count": c.down(count, ICP_ITERATIONS),
                 "dev_rms": c.down(rms, ICP_ITERATIONS), "dev_partner": c.down(partner, m)})
     return out
