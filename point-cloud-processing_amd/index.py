@@ -607,6 +607,40 @@ class Index:
                                                    _capi.PCPX_OUTLIERS_ON_DEVICE,
                                                    *(self._dptr(d) for d in (d_keep, d_kept_rows, d_kept_count, d_count, d_stats))))
 
+    # ---- boundary points (include/pcpx_boundary.h) ----
+    def boundary(self, normals, radius, gap_sectors=16, min_neighbours=1, want_keep=False, want_gap=False, want_counts=False,
+                 want_sectors=False):
+        """Boundary points by the angle criterion (PCL's BoundaryEstimation): the rim of an open surface, the edges of its holes.  The
+        directions from a point to the points of its sphere (the rule of range_count_self) are projected into the plane of its normal
+        (`normals`: n_in x 3, float32, used as given) and sorted into 64 sectors of 5.625 degrees; G is the longest cyclic run of
+        empty sectors.  A point is kept iff it is indexed, its normal is finite and not zero, its sphere holds at least
+        max(min_neighbours, 1) points and G >= gap_sectors (1 .. 64; 16: an empty angle of 90 degrees or more).  Exact: every bit
+        depends on the cloud and the normals alone (include/pcpx_boundary.h).
+        Returns the kept input indices, ascending (uint32)[, the keep mask bool (n_in,)][, uint8 (n_in, 2): G and the sector the gap
+        starts at, 255 255 where there is no frame][, the counts uint32 (n_in,)][, the sector masks uint64 (n_in,)]."""
+        nrm = _f32(normals, 3)
+        if len(nrm) != self.n_in:
+            raise ValueError("one normal per input point")
+        keep = np.empty(self.n_in, np.uint8)
+        kept = np.empty(self.n_in, np.uint32)
+        gap =np.empty((self.n_in, 2), np.uint8) if want_gap else None
+        cnt = np.empty(self.n_in, np.uint32) if want_counts else None
+        sectors = np.empty(self.n_in, np.uint64) if want_sectors else None
+        count = C.c_uint64(0)
+        check(self._lib.pcpx_boundary_self(self._h, _vp(nrm), float(radius), int(gap_sectors), int(min_neighbours), 0, _vp(keep), _vp(kept),
+                                           C.byref(count), _vp(gap), _vp(cnt), _vp(sectors)))
+        return self._outlier_result(kept, count, keep, want_keep, gap, cnt, sectors)
+
+    def boundary_dev(self, d_normals, radius, d_keep, gap_sectors=16, min_neighbours=1, d_kept_rows=None, d_kept_count=None, d_gap=None,
+                     d_count=None, d_sectors=None):
+        """Device form (torch tensors or pointers to device arrays: normals float32 n_in x 3 and keep uint8 by input row, kept_rows
+        uint32 with room for n_in entries, d_kept_count one uint64, d_gap uint8 n_in x 2, d_count uint32 and d_sectors uint64 by
+        input row), enqueued on the index's stream with no synchronisation: the normals that range_neighbourhoods_self_dev left on the
+        device go straight in, and the kept rows straight on into Index.from_device and cluster."""
+        check(self._lib.pcpx_boundary_self(self._h, self._dptr(d_normals), float(radius), int(gap_sectors), int(min_neighbours),
+                                           _capi.PCPX_BOUNDARY_ON_DEVICE,
+                                           *(self._dptr(d) for d in (d_keep, d_kept_rows, d_kept_count, d_gap, d_count, d_sectors))))
+
     # ---- descriptors (include/pcpx_descriptors.h) ----
     def fpfh(self, normals, radius, rows=None, want_spfh=False):
         """Fast Point Feature Histograms (Rusu et al. 2009) over `radius` from `normals` (n_in x 3, float32, used as given): 33 floats
