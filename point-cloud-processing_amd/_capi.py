@@ -58,6 +58,11 @@ class VoxelParams(C.Structure):
     _fields_ = [("leaf", C.c_float * 3), ("origin", C.c_float * 3), ("flags", C.c_uint32), ("attr_columns", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class ObjectsParams(C.Structure):
+    """pcpx_objects_params (include/pcpx_objects.h)."""
+    _fields_ = [("flags", C.c_uint32), ("none_label", C.c_uint32), ("min_size", C.c_uint32), ("max_size", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 K_BUILD, K_KNN, K_NORMALS, K_RANGE, K_QUERY_PREP = range(5)
 
 
@@ -380,6 +385,18 @@ BOUNDARY_SIGNATURES = {
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/pcpx_objects.h (objects from labels)
+PCPX_OBJECTS_ON_DEVICE = 1
+PCPX_OBJECTS_SKIP = 2
+PCPX_OBJECTS_NONE = 0xFFFFFFFF
+PCPX_OBJECTS_CHUNK = 64
+_pop = C.POINTER(ObjectsParams)
+OBJECTS_SIGNATURES = {
+    "pcpx_objects_plan": (C.c_int, [C.c_uint64, C.c_uint64, u64p, u64p]),
+    "pcpx_label_objects": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, _pop, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 
 def load():
     """Load libpcpx.so; raises if it has not been built (run __graft_entry__.build())."""
@@ -397,7 +414,7 @@ def load():
             + list(KEYPOINTS_SIGNATURES.items()) + list(DESCRIPTORS_SIGNATURES.items()) + list(MATCH_SIGNATURES.items())\
             + list(REGISTER_SIGNATURES.items()) + list(ICP_SIGNATURES.items()) + list(PLANES_SIGNATURES.items())\
             + list(VOXEL_SIGNATURES.items()) + list(MLS_SIGNATURES.items()) + list(OUTLIERS_SIGNATURES.items())\
-            + list(BOUNDARY_SIGNATURES.items()):
+            + list(BOUNDARY_SIGNATURES.items()) + list(OBJECTS_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args
