@@ -426,6 +426,11 @@ int pcpx_debug_eps_test_mode(pcpx_index* idx, int mode);
  * groups out by the times that launch recorded, the longest first; "gather_outputs" (default 0: measured slower): input-order
  * normals and counts are written at curve positions and permuted by a gather instead of being scattered from the search kernel;
  * "gather_counts" (default 0: measured slower as well): the same for pcpx_range_count_self_dev's counts.
+ * "fps_bucket_height" (0 = automatic, the default; 1, 2, 3; anything else is PCPX_ERR_INVALID): the height of the tree node whose
+ * leaf slots pcpx_farthest_points_self treats as one bucket (32, 128 or 512 slots); "fps_prune" (default 1): 0 = every sample
+ * updates every bucket instead of only those whose box is nearer than their largest distance; "fps_one_block" (-1 = automatic, the
+ * default; 0; 1): the whole selection in one launch of one workgroup, for a cloud that fits into its registers (8192 leaf slots),
+ * instead of one launch per sample (pcpx_fps.h).
  * "poison" (a byte, 0 ... 255; anything else is PCPX_ERR_INVALID) is a test switch, not a setting: it waits for the handle's stream,
  * fills everything that is scratch by contract with that byte -- the handle's scratch block, its k > 32 pass keys, its
  * per-position gather scratch, its input-index table while that is not valid, its recorded group times and order while nothing is

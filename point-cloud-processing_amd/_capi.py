@@ -58,6 +58,11 @@ class VoxelParams(C.Structure):
     _fields_ = [("leaf", C.c_float * 3), ("origin", C.c_float * 3), ("flags", C.c_uint32), ("attr_columns", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class FpsParams(C.Structure):
+    """pcpx_fps_params (include/pcpx_fps.h)."""
+    _fields_ = [("flags", C.c_uint32), ("start", C.c_uint32), ("stop_radius", C.c_float), ("reserved", C.c_uint32)]
+
+
 class ObjectsParams(C.Structure):
     """pcpx_objects_params (include/pcpx_objects.h)."""
     _fields_ = [("flags", C.c_uint32), ("none_label", C.c_uint32), ("min_size", C.c_uint32), ("max_size", C.c_uint32), ("reserved", C.c_uint32)]
@@ -397,6 +402,15 @@ OBJECTS_SIGNATURES = {
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/pcpx_fps.h (farthest point sampling)
+PCPX_FPS_ON_DEVICE = 1
+PCPX_FPS_NONE = 0xFFFFFFFF
+PCPX_FPS_START_LOWEST = 0xFFFFFFFF
+FPS_SIGNATURES = {
+    "pcpx_farthest_points_self": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(FpsParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
+}
+
 
 def load():
     """Load libpcpx.so; raises if it has not been built (run __graft_entry__.build())."""
@@ -414,7 +428,7 @@ def load():
             + list(KEYPOINTS_SIGNATURES.items()) + list(DESCRIPTORS_SIGNATURES.items()) + list(MATCH_SIGNATURES.items())\
             + list(REGISTER_SIGNATURES.items()) + list(ICP_SIGNATURES.items()) + list(PLANES_SIGNATURES.items())\
             + list(VOXEL_SIGNATURES.items()) + list(MLS_SIGNATURES.items()) + list(OUTLIERS_SIGNATURES.items())\
-            + list(BOUNDARY_SIGNATURES.items()) + list(OBJECTS_SIGNATURES.items()):
+            + list(BOUNDARY_SIGNATURES.items()) + list(OBJECTS_SIGNATURES.items()) + list(FPS_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

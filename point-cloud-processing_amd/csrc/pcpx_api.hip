@@ -1059,6 +1059,16 @@ int pcpx_debug_set(pcpx_index* h, const char* name, int64_t value)
         ix->tuning.icp_resort = value != 0;
     } else if (key == "icp_previous_start") {
         ix->tuning.icp_previous_start = value < 0 ? -1 : value != 0;
+    } else if (key == "fps_bucket_height") {
+        if (value < 0 || value > 3) {
+            set_error("pcpx_debug_set: fps_bucket_height is 0 (automatic), 1, 2 or 3");
+            return PCPX_ERR_INVALID;
+        }
+        ix->tuning.fps_bucket_height = static_cast<int>(value);
+    } else if (key == "fps_prune") {
+        ix->tuning.fps_prune = value != 0;
+    } else if (key == "fps_one_block") {
+        ix->tuning.fps_one_block = value < 0 ? -1 : value != 0;
     } else if (key == "poison") {
         if (value < 0 || value > 255) {
             set_error("pcpx_debug_set: poison takes a byte, 0 ... 255");

@@ -274,6 +274,10 @@ struct Index {
                                   // switch: the results do not depend on the source order)
         int icp_previous_start = -1;  // pcpx_icp.hip: from the second round on a lane starts from its previous partner (1), from nothing
                                       // (0), or as that file's default says (-1); the results are the same
+        int fps_bucket_height = 0;    // pcpx_fps.hip: the tree height of a bucket, 1 .. 3; 0: as that file's default says
+        int fps_prune = 1;            // pcpx_fps.hip: 0 = a sample updates every bucket (an A/B switch: the prune test only skips work)
+        int fps_one_block = -1;       // pcpx_fps.hip: the whole loop in one launch of one workgroup: 1 = wherever the cloud fits, 0 = never,
+                                      // -1 = as that file's default says
     } tuning;
     int eps_test_mode = 0;  // k_knn's eps-box test: 0 = where it is cheaper (query.hip: eps_box_threshold), 1 = in the compaction, 2 = per candidate
 

@@ -641,6 +641,55 @@ class Index:
                                            _capi.PCPX_BOUNDARY_ON_DEVICE,
                                            *(self._dptr(d) for d in (d_keep, d_kept_rows, d_kept_count, d_gap, d_count, d_sectors))))
 
+    # ---- farthest point sampling (include/pcpx_fps.h) ----
+    @staticmethod
+    def _fps_params(flags, start, stop_radius):
+        return _capi.FpsParams(flags, _capi.PCPX_FPS_START_LOWEST if start is None else int(start), float(stop_radius), 0)
+
+    def farthest_points(self, m, start=None, stop_radius=0.0, want_d2=False, want_min_d2=False, want_owner=False, want_evaluations=False):
+        """Farthest point sampling: up to `m` indexed points, each the one farthest (squared distance by the rule of
+        range_count_self; among equals the lowest input index) from the samples before it, from `start` on (an input row; None: the
+        lowest indexed row; a row outside the voxel grid selects nothing).  The selection ends early when no point is farther than
+        `stop_radius` from the samples -- with 0, when every point coincides with a sample.  Exact: every bit depends on the cloud
+        and the arguments alone (include/pcpx_fps.h).
+        Returns the selected input indices in selection order (uint32, count of them)[, float32 (count,): each sample's squared
+        distance to the samples before it, the first +inf][, float32 (n_in,): every row's squared distance to its nearest sample,
+        +inf outside the grid][, uint32 (n_in,): the ordinal of the earliest nearest sample, 0xFFFFFFFF outside the grid][, the
+        number of squared distances formed: a diagnostic]."""
+        m = int(m)
+        most = min(m, self.n_in)
+        rows = np.empty(max(most, 1), np.uint32)  # (never NULL: m > 0 on an empty cloud is a valid call)
+        d2 = np.empty(most, np.float32) if want_d2 else None
+        min_d2 = np.empty(self.n_in, np.float32) if want_min_d2 else None
+        owner = np.empty(self.n_in, np.uint32) if want_owner else None
+        count, evaluations = C.c_uint64(0), C.c_uint64(0)
+        params = self._fps_params(0, start, stop_radius)
+        # (the library writes [0, count), count <= min(m, indexed points): arrays of min(m, n_in) entries hold them)
+        check(self._lib.pcpx_farthest_points_self(self._h, m, C.byref(params), _vp(rows),
+                                                  C.addressof(count), _vp(d2), _vp(min_d2), _vp(owner),
+                                                  C.addressof(evaluations) if want_evaluations else None))
+        k = int(count.value)
+        out = (rows[:k].copy(),)
+        if want_d2:
+            out += (d2[:k].copy(),)
+        if want_min_d2:
+            out += (min_d2,)
+        if want_owner:
+            out += (owner,)
+        if want_evaluations:
+            out += (int(evaluations.value),)
+        return out[0] if len(out) == 1 else out
+
+    def farthest_points_dev(self, m, d_rows, d_count, start=None, stop_radius=0.0, d_d2=None, d_min_d2=None, d_owner=None, d_evaluations=None):
+        """Device form (torch tensors or pointers to device arrays: d_rows uint32 and d_d2 float32 with room for m entries, of which
+        [0, count) are written; d_count and d_evaluations one uint64 each; d_min_d2 float32 and d_owner uint32 by input row),
+        enqueued on the index's stream: min(m, indexed points) launches and a few more, no read-back and no synchronisation between
+        samples -- the stop rule is applied on the device.  The rows go straight on into a gather for a torch model or into
+        Index.from_device."""
+        params = self._fps_params(_capi.PCPX_FPS_ON_DEVICE, start, stop_radius)
+        check(self._lib.pcpx_farthest_points_self(self._h, int(m), C.byref(params),
+                                                  *(self._dptr(d) for d in (d_rows, d_count, d_d2, d_min_d2, d_owner, d_evaluations))))
+
     # ---- descriptors (include/pcpx_descriptors.h) ----
     def fpfh(self, normals, radius, rows=None, want_spfh=False):
         """Fast Point Feature Histograms (Rusu et al. 2009) over `radius` from `normals` (n_in x 3, float32, used as given): 33 floats
@@ -882,7 +931,7 @@ class Index:
         return out
 
     def debug_set(self, name, value):
-        """pcpx_debug_set: 'long_groups_first', 'gather_outputs', 'icp_resort' (how work is done, never what comes out); 'poison' (a byte):
+        """pcpx_debug_set: 'long_groups_first', 'gather_outputs', 'icp_resort', 'fps_bucket_height', 'fps_prune', 'fps_one_block' (how work is done, never what comes out); 'poison' (a byte):
         fills everything that is scratch by contract, of the handle, its device's pool and the idle index blocks (include/pcpx.h)."""
         check(self._lib.pcpx_debug_set(self._h, name.encode(), int(value)))
 
