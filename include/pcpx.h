@@ -42,6 +42,18 @@
  *   - A call writes only inside the documented extents of its outputs.
  *   - There is no CPU fallback: without a usable HIP device every compute entry point fails
  *     with PCPX_ERR_DEVICE.
+ *   - Threads: any entry point may be called from any host thread at any time; the library keeps no thread affinity and a
+ *     handle may be used by a thread other than the one that made it.  Calls on ONE handle (pcpx_index, pcpx_kd) run one at
+ *     a time: a second thread's call waits inside the library until the first has returned.  Destroying a handle is the one
+ *     exception: no call on it may be running or begin once pcpx_index_destroy / pcpx_kd_destroy has it.  The entry points
+ *     that take a device number instead of a handle and stage through that device's shared pool (the host-pointer forms
+ *     without a handle, and the
+ *     handle-less `*_dev` forms whose scratch is a block of that pool) run one at a time PER DEVICE.  Handles are
+ *     independent of one another: calls on different handles overlap, on one stream or on several, and what one handle frees
+ *     is given to another only once the work that used it has completed.  Two things are per THREAD, never per process: the
+ *     text of pcpx_last_error() -- a failure on one thread neither sets nor clears what another thread reads, and a later
+ *     success on the same thread leaves it in place -- and the current device, which every entry point restores for the
+ *     calling thread alone.  Outputs of concurrent calls must not overlap; that is the caller's to ensure.
  */
 #ifndef PCPX_H
 #define PCPX_H

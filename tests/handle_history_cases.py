@@ -172,7 +172,7 @@ class Ctx:
         a = np.ascontiguousarray(a).reshape(-1)
         a = a.view({np.dtype(np.uint32): np.int32, np.dtype(np.uint64): np.int64}.get(a.dtype, a.dtype))
         d = t.from_numpy(a.copy() if len(a) else np.zeros(1, a.dtype)).to(t.device("cuda", 0))
-        t.cuda.synchronize()  # (torch's stream is not the handle's)
+        t.cuda.synchronize(0)  # (torch's stream is not the handle's; device 0 by number: a caller's thread may have another current)
         return d
 
     def out(self, length, kind):
@@ -182,7 +182,7 @@ class Ctx:
         return t.full((max(int(length), 1),), FILL, dtype=dtype, device=t.device("cuda", 0))
 
     def ready(self):
-        self.torch().cuda.synchronize()  # (the fills are on torch's stream, a handle's call on its own)
+        self.torch().cuda.synchronize(0)  # (the fills are on torch's stream, a handle's call on its own)
 
     def drain(self):
         """after the calls on the handle: its stream is drained before an output is looked at"""
