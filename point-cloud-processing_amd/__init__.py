@@ -3,12 +3,14 @@
 The compute path is libpcpx.so (hand-written HIP for gfx950, C ABI in include/pcpx.h); importing the
 package does not load it, using any compute entry point does and fails loudly if it is missing.
 """
-from . import match, objects, planes, ply, register, simplify, surface, synthetic, voxel  # noqa: F401
+from . import match, objects, planes, ply, register, shapes, simplify, surface, synthetic, voxel  # noqa: F401
 from ._capi import Grid3d  # noqa: F401
 from .match import match_correspondences, match_correspondences_dev, match_nearest, match_nearest_dev, match_plan  # noqa: F401
 from .objects import label_objects, label_objects_dev, objects_plan  # noqa: F401
 from .planes import extract_planes, extract_planes_dev, plane_fit, plane_fit_dev, plane_plan, ransac_plane, ransac_plane_dev  # noqa: F401
 from .register import ransac_plan, ransac_rigid, ransac_rigid_dev, rigid_fit, rigid_fit_dev  # noqa: F401
+from .shapes import (cylinder_fit, ransac_cylinder, ransac_shape_dev, ransac_sphere, shape_fit_dev, shape_params, shape_plan,  # noqa: F401
+                     sphere_fit)
 from .simplify import hierarchy_simplification, hierarchy_simplification_dev  # noqa: F401
 from .surface import regular_grid_containing, surface_nets, surface_nets_from_hint  # noqa: F401
 from .voxel import voxel_grid, voxel_grid_dev, voxel_plan  # noqa: F401
@@ -25,4 +27,5 @@ __all__ = ["Index", "LinkedOctree", "LinkedKdTree", "KdTreeK", "PcpxError", "bou
            "register", "ransac_plan", "ransac_rigid", "ransac_rigid_dev", "rigid_fit", "rigid_fit_dev",
            "planes", "plane_plan", "ransac_plane", "ransac_plane_dev", "plane_fit", "plane_fit_dev", "extract_planes", "extract_planes_dev",
            "voxel", "voxel_grid", "voxel_grid_dev", "voxel_plan",
-           "objects", "label_objects", "label_objects_dev", "objects_plan"]
+           "objects", "label_objects", "label_objects_dev", "objects_plan",
+           "shapes", "shape_params", "shape_plan", "ransac_sphere", "ransac_cylinder", "ransac_shape_dev", "sphere_fit", "cylinder_fit", "shape_fit_dev"]

@@ -53,6 +53,13 @@ class PlaneParams(C.Structure):
                 ("min_inliers", C.c_uint32), ("max_planes", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class ShapeParams(C.Structure):
+    """pcpx_shape_params (include/pcpx_shapes.h)."""
+    _fields_ = [("hypotheses", C.c_uint64), ("kind", C.c_uint32), ("seed", C.c_uint32), ("flags", C.c_uint32), ("max_distance", C.c_float),
+                ("min_radius", C.c_float), ("max_radius", C.c_float), ("min_normal_sin", C.c_float), ("min_normal_cos", C.c_float),
+                ("axis", C.c_float * 3), ("min_axis_cos", C.c_float), ("origin_row", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class VoxelParams(C.Structure):
     """pcpx_voxel_params (include/pcpx_voxel.h)."""
     _fields_ = [("leaf", C.c_float * 3), ("origin", C.c_float * 3), ("flags", C.c_uint32), ("attr_columns", C.c_uint32), ("reserved", C.c_uint32)]
@@ -411,6 +418,25 @@ FPS_SIGNATURES = {
                                             C.c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/pcpx_shapes.h (sphere and cylinder detection)
+PCPX_SHAPE_SPHERE = 1
+PCPX_SHAPE_CYLINDER = 2
+PCPX_SHAPE_REFIT = 1
+PCPX_SHAPE_NORMALS = 2
+PCPX_SHAPE_AXIS = 4
+PCPX_SHAPE_ON_DEVICE = 8
+PCPX_SHAPE_ORIGIN_FIRST = 0xFFFFFFFF
+PCPX_SHAPE_FIT_OK = 0
+PCPX_SHAPE_FIT_DEGENERATE = 1
+_psp = C.POINTER(ShapeParams)
+SHAPES_SIGNATURES = {
+    "pcpx_shape_plan": (C.c_int, [C.c_uint64, C.c_uint64, u32p, u64p, u64p]),
+    "pcpx_shape_ransac": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, _psp, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pcpx_shape_fit": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 
 def load():
     """Load libpcpx.so; raises if it has not been built (run __graft_entry__.build())."""
@@ -428,7 +454,8 @@ def load():
             + list(KEYPOINTS_SIGNATURES.items()) + list(DESCRIPTORS_SIGNATURES.items()) + list(MATCH_SIGNATURES.items())\
             + list(REGISTER_SIGNATURES.items()) + list(ICP_SIGNATURES.items()) + list(PLANES_SIGNATURES.items())\
             + list(VOXEL_SIGNATURES.items()) + list(MLS_SIGNATURES.items()) + list(OUTLIERS_SIGNATURES.items())\
-            + list(BOUNDARY_SIGNATURES.items()) + list(OBJECTS_SIGNATURES.items()) + list(FPS_SIGNATURES.items()):
+            + list(BOUNDARY_SIGNATURES.items()) + list(OBJECTS_SIGNATURES.items()) + list(FPS_SIGNATURES.items())\
+            + list(SHAPES_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

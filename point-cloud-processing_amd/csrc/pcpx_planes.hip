@@ -5,7 +5,7 @@
 //   k_plane_begin    the words of the call's state: the number of live records, done = 0
 //   k_plane_pack     rows -> 16-byte records {x - o, row}, 32-byte ones {x - o, row, N, 0} under the normal gate, NaN-marked
 //   k_plane_count    one wavefront per (64 consecutive hypotheses, one segment of the live records): one count per lane
-//   k_plane_fold     a hypothesis's segment counts into one word
+//   k_plane_fold     (pcpx_ransac.h) a hypothesis's segment counts into one word
 //   k_ransac_best    (pcpx_ransac.h) the best key
 //   k_plane_decide   one thread: the winner rebuilt by the same device function, found / stop, the plane in float64
 //   k_plane_flag     the inlier flag and the keep flag of every live record, the label of the inliers' rows
@@ -31,7 +31,6 @@ namespace pcpx {
 
 namespace {
 
-constexpr u32 PL_FOLD = 16;  // lanes of k_plane_fold that share a hypothesis
 constexpr u32 PL_WAVES = 4;  // waves of a k_plane_count block: four consecutive hypothesis groups on one segment (they share its records in the scalar cache)
 // (the plan -- segment_plan and its constants --: pcpx_ransac.h)
 // the doubles of the fit's state: [0] the number of usable rows, [1..3] the sums, [4..6] the centroid, [8..13] the scatter,
@@ -67,13 +66,6 @@ struct State {
     Plane win;
     double hyp[4];
 };
-__device__ __forceinline__ bool gone(const u32* done, u32 round)
-{
-    if (!done) return false;
-    const u32 d = *done;
-    return d != 0u && d <= round;
-}
-
 struct Layout {
     SegmentPlan plan;
     size_t rec[2] = {0, 0}, counts = 0, key = 0, flag = 0, keep = 0, place = 0, sums = 0, positions = 0, rowsout = 0, npos = 0, state = 0, fit = 0, bytes = 0;
@@ -267,26 +259,6 @@ __global__ __launch_bounds__(64 * PL_WAVES) void k_plane_count(const RecOf<NORMA
     }
     for (; t < t1; ++t) n += inlier(pl, load_const(rec + t), tau, cosn) ? 1u : 0u;
     if (active) counts[static_cast<u64>(blockIdx.y) * T + h] = valid ? n : RG_INVALID;
-}
-
-// PL_FOLD lanes per hypothesis: counts[h] (segment 0's row) becomes the sum over all segments, so that k_ransac_best reads one word
-// per hypothesis.  (Its own loop over the segments is one thread's chain of loads: with 245 segments and 1 024 hypotheses -- a
-// single block -- it took 0.23 ms a round, a third of an extraction)  Integer sums: exact in any order.  An
-// invalid hypothesis keeps RG_INVALID.  The group's lanes all read counts[h] before lane 0 of the group writes it.
-__global__ __launch_bounds__(RG_BLOCK) void k_plane_fold(u32* counts, const u32* __restrict__ done, u32 round, u64 h_base, u64 h_end, u64 T, u32 segments)
-{
-    if (gone(done, round)) return;
-    const u64 h = h_base + (static_cast<u64>(blockIdx.x) * RG_BLOCK + threadIdx.x) / PL_FOLD;
-    const u32 part = threadIdx.x % PL_FOLD;
-    const bool in = h < h_end;
-    const u32 first = in ? counts[h] : RG_INVALID;
-    u32 sum = 0;
-    if (first != RG_INVALID) {
-        for (u32 s = part ? part : PL_FOLD; s < segments; s += PL_FOLD) sum += counts[static_cast<u64>(s) * T + h];
-    }
-#pragma unroll
-    for (u32 off = PL_FOLD / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
-    if (part == 0 && first != RG_INVALID) counts[h] = first + sum;
 }
 
 // One thread.  The round's winner from the best key: found, and whether the loop stops here (nothing valid, or a score below
@@ -552,7 +524,7 @@ int planes_device(const Layout& L, char* base, const Cloud& in, const pcpx_plane
                 const dim3 grid(blocks_of((here + GROUP - 1) / GROUP, PL_WAVES), L.plan.segments);
                 k_plane_count<NORMALS><<<grid, 64 * PL_WAVES, 0, s>>>(rec[cur], cap, &st->live[cur], &st->done, round, h0, T, seed, gate, a.max_distance,
                                                                      a.min_normal_cos, L.plan.rows, counts);
-                if (L.plan.segments > 1) k_plane_fold<<<blocks_of(here * PL_FOLD, RG_BLOCK), RG_BLOCK, 0, s>>>(counts, &st->done, round, h0, h0 + here, T, L.plan.segments);
+                if (L.plan.segments > 1) k_plane_fold<PL_FOLD><<<blocks_of(here * PL_FOLD, RG_BLOCK), RG_BLOCK, 0, s>>>(counts, &st->done, round, h0, h0 + here, T, L.plan.segments);
                 k_ransac_best<<<blocks_of(here, RG_BLOCK * RG_BEST_PER_THREAD), RG_BLOCK, 0, s>>>(counts, h0, h0 + here, T, 1u, key);
             }
         }
