@@ -198,7 +198,7 @@ int pcpx_knn_self_strided_dev(pcpx_index* idx, uint32_t k, float eps, uint64_t s
 int pcpx_knn_self_curve_order_dev(pcpx_index* idx, uint32_t k, float eps, uint64_t sorted_first, uint64_t sorted_count,
                                   uint32_t* d_out_idx, uint32_t* d_out_count, float* d_opt_d2, float* d_opt_normals);
 /* The curve order itself: d_out_perm[p] = input index of the p-th point (pcpx_index_size entries; a rank-local handle: the
- * entries of its core only, at their global positions), d_opt_out_position_of[i] = position of input point i (n entries,
+ * entries of its shard only, at their global positions; its position table holds 0xFFFFFFFF for every other point), d_opt_out_position_of[i] = position of input point i (n entries,
  * 0xFFFFFFFF for a point that is not indexed).  Either may be NULL.  Enqueued on the handle's stream. */
 int pcpx_index_perm_dev(pcpx_index* idx, uint32_t* d_out_perm, uint32_t* d_opt_out_position_of);
 
@@ -464,6 +464,26 @@ int pcpx_debug_group_times(pcpx_index* idx, uint32_t* out_ticks, uint64_t capaci
 /* Diagnostic access to the build's radix sort: stable sort of 64-bit words by their bits [first_bit, 64)
  * (first_bit a multiple of 8): words that agree on those bits keep their input order. */
 int pcpx_debug_sort_keys(const uint64_t* keys, uint64_t n, int first_bit, int device, uint64_t* out_keys);
+/* FOR TESTS ONLY (tests/test_gpu_build_order.py): the structure the handle's last build left, copied to host arrays after waiting
+ * for the handle's stream.  It changes nothing and no query needs it; its layout follows the internal one and may change with it.
+ *   out_shape (PCPX_DEBUG_TREE_SHAPE_WORDS entries, always filled): [0] indexed points, [1] leaf records, [2] depth of the tree
+ *     (leaves are level `depth`; never 1), [3] nodes of the heap that are copied: level_start(depth) + written(depth) with
+ *     level_start(d) = (4^d - 1) / 3, or 0 for an empty index, [4 + d] written(d): the nodes of level d the build writes, d = 0 ...
+ *     depth -- the real nodes of the level and the padding siblings that complete its last group of four (1 for the root);
+ *   out_leaves: [1] records of 32 words: x[8], y[8], z[8] (float32; NaN in a padding slot), id[8] (input index; 0xFFFFFFFF in a
+ *     padding slot), in curve order;
+ *   out_nodes: [3] records of 8 words in heap order: lo[3], hi[3] (float32), poison (+0: a real node, NaN: a padding node), 0.
+ *     DEFINED are written(d) nodes from level_start(d) of every level d <= depth, and [1] leaf records; what lies between the
+ *     levels' written extents is whatever the memory held;
+ *   out_first_pass: 256 entries, per top digit of the sort word the first bucketed radix pass its bucket took in the last build's
+ *     sort (1: every pass; 3: the bucket stopped after bits [40, 64) and the leaf kernel ordered its runs); all zeros when that
+ *     build ran no sort in finish mode (no points).
+ * PCPX_ERR_CAPACITY (out_shape filled, nothing else written) if out_leaves / out_nodes / out_first_pass is NULL or a capacity
+ * (in records) is below [1] / [3].  A rank-local handle answers for its local tree: [0] is its local point count, ids are global
+ * input indices. */
+#define PCPX_DEBUG_TREE_SHAPE_WORDS 20
+int pcpx_debug_tree(pcpx_index* idx, uint64_t* out_shape, void* out_leaves, uint64_t leaf_capacity, void* out_nodes, uint64_t node_capacity,
+                    uint32_t* out_first_pass);
 int pcpx_profile_begin(pcpx_index* idx);
 int pcpx_profile_end(pcpx_index* idx, pcpx_profile* out);
 

@@ -171,6 +171,7 @@ SIGNATURES = {
     "pcpx_debug_knn_stats": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, u64p, C.c_uint64]),
     "pcpx_debug_eps_test_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "pcpx_debug_sort_keys": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p]),
+    "pcpx_debug_tree": (C.c_int, [C.c_void_p, u64p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, u32p]),
     "pcpx_profile_begin": (C.c_int, [C.c_void_p]),
     "pcpx_profile_end": (C.c_int, [C.c_void_p, C.POINTER(Profile)]),
     "pcpx_kd_create": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),

@@ -1194,6 +1194,41 @@ int pcpx_debug_sort_keys(const uint64_t* keys, uint64_t n, int first_bit, int de
     });
 }
 
+// (for tests: include/pcpx.h)
+int pcpx_debug_tree(pcpx_index* h, uint64_t* out_shape, void* out_leaves, uint64_t leaf_capacity, void* out_nodes, uint64_t node_capacity,
+                    uint32_t* out_first_pass)
+{
+    return on_index(h, "pcpx_debug_tree", ANY_INDEX, [&](Index* ix) -> int {
+    if (!out_shape) return PCPX_ERR_INVALID;
+    static_assert(PCPX_DEBUG_TREE_SHAPE_WORDS == 4 + MAXDEPTH + 1, "one word per level");
+    u32 nleaves = 0, written[MAXDEPTH + 1];
+    int depth = 0;
+    build_tree_shape(static_cast<u32>(ix->n), &nleaves, &depth, written);
+    const u64 level0 = ((1ull << (2 * depth)) - 1ull) / 3ull;  // heap id of the first node of level `depth`
+    const u64 nnodes = nleaves ? level0 + written[depth] : 0;
+    out_shape[0] = ix->n;
+    out_shape[1] = nleaves;
+    out_shape[2] = static_cast<u64>(depth);
+    out_shape[3] = nnodes;
+    for (int d = 0; d <= MAXDEPTH; ++d) out_shape[4 + d] = written[d];
+    if (nleaves != ix->nleaves || depth != ix->depth || nnodes > ix->nodes_cap) {
+        set_error("pcpx_debug_tree: internal error, the handle's tree is not the shape of its point count");
+        return PCPX_ERR_DEVICE;
+    }
+    if (!out_leaves || !out_nodes || !out_first_pass || leaf_capacity < nleaves || node_capacity < nnodes) return PCPX_ERR_CAPACITY;
+    const hipStream_t s = ix->stream;
+    const bool finish_sort = ix->finish_words && ix->n_in > 0;  // (a build of no points runs no sort: the pointers are an earlier build's)
+    if (finish_sort) PCPX_HIP(hipMemcpyAsync(out_first_pass, ix->finish_first_pass, 256 * sizeof(u32), hipMemcpyDeviceToHost, s));
+    else std::memset(out_first_pass, 0, 256 * sizeof(u32));
+    if (nleaves) {
+        PCPX_HIP(hipMemcpyAsync(out_leaves, ix->d_leaves, static_cast<size_t>(nleaves) * sizeof(Leaf), hipMemcpyDeviceToHost, s));
+        PCPX_HIP(hipMemcpyAsync(out_nodes, ix->d_nodes, static_cast<size_t>(nnodes) * sizeof(NodeBox), hipMemcpyDeviceToHost, s));
+    }
+    PCPX_HIP(hipStreamSynchronize(s));
+    return PCPX_OK;
+    });
+}
+
 int pcpx_profile_begin(pcpx_index* h)
 {
     return on_index(h, "pcpx_profile_begin", ANY_INDEX, [&](Index* ix) -> int {

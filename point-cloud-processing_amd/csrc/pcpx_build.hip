@@ -335,13 +335,12 @@ __host__ __device__ inline u32 finish_blocks(const TreeShape& ts)
 // that agree on those bits -- a handful each -- in arbitrary... no: in input order.  A block takes the FILL_SLOTS words of its tile
 // and FIN_MARGIN on either side into LDS, finds the runs (neighbours that agree above their bucket's shift), and every word counts
 // the words of its run that are smaller: that is its place.  Two global radix passes (16 B/point each) and their look-back chains
-// become ~50 LDS reads per word.  A run longer than FIN_MARGIN -- a cell far denser than its bucket's fullest 16-bit cell
-// suggested -- cannot be ordered here: the block notes the bucket in `redo` and the host repeats the sort with that bucket taking
+// become ~50 LDS reads per word.  A run longer than FIN_RUN_MAX = FIN_MARGIN + 1 words (pcpx_internal.h) -- a cell far denser than its
+// bucket's fullest 16-bit cell suggested -- cannot be ordered here: the block notes the bucket in `redo` and the host repeats the sort with that bucket taking
 // every pass (the handle remembers it).  Buckets that took every pass have nothing to order: their runs are ties on all sorted
 // bits, which the stable passes left in input order.  The ordered words themselves are not written back: what searches the sorted
 // words afterwards (prepare_queries' seeds, the rank-local build's core) needs them ordered on their top 24 bits only, which the
 // prefix-sorted words are (Index::sorted_codes).
-constexpr int FIN_MARGIN = 64;
 constexpr int FIN_WINDOW = FILL_SLOTS + 2 * FIN_MARGIN;  // words of the window; + one word on either side to see whether its ends start runs
 struct FinishArgs {
     const u64* words;              // prefix-sorted words, or nullptr: `sorted` holds fully sorted words (nothing to order)
@@ -426,9 +425,10 @@ __global__ __launch_bounds__(FILL_BLOCK) void k_finish(const float4* __restrict_
             const bool in_tile = j > FIN_MARGIN && j <= FIN_MARGIN + FILL_SLOTS;
             u32 a = j, smaller = 0, steps = 0;
             bool whole = true;
+            // (`steps` counts the other words of the run, before and behind: FIN_RUN_MAX - 1 of them at most)
 #pragma nounroll  // (bounded by FIN_MARGIN, hipcc would write all 64 trips out, each with a saved lane mask of its own)
             while (!starts[a]) {  // (starts[0] is always set: reaching it means the run began out of sight)
-                if (++steps > FIN_MARGIN) {
+                if (++steps >= FIN_RUN_MAX) {
                     whole = false;
                     break;
                 }
@@ -439,7 +439,7 @@ __global__ __launch_bounds__(FILL_BLOCK) void k_finish(const float4* __restrict_
             u32 b = j + 1u;
 #pragma nounroll
             while (whole && !starts[b]) {  // (b <= FIN_WINDOW + 1 whenever this is evaluated)
-                if (b == FIN_WINDOW + 1u || ++steps > FIN_MARGIN) {
+                if (b == FIN_WINDOW + 1u || ++steps >= FIN_RUN_MAX) {
                     whole = false;
                     break;
                 }
@@ -824,6 +824,13 @@ int build_tree_from_sorted(Index& ix, u32 n_at_most, bool count_on_device)
         k_upper_levels<<<upper_blocks(ts, c, levels), UPPER_BLOCK, 0, s>>>(ix.d_nodes, bc, stage);
     }
     return check_hip(hipGetLastError(), "tree kernels", __FILE__, __LINE__);
+}
+void build_tree_shape(u32 nvalid, u32* nleaves, int* depth, u32 (&written)[MAXDEPTH + 1])
+{
+    const TreeShape ts = shape_of(nvalid);
+    *nleaves = ts.nleaves;
+    *depth = ts.depth;
+    for (int d = 0; d <= MAXDEPTH; ++d) written[d] = (ts.nleaves > 0 && d <= ts.depth) ? ts.nwrite(d) : 0u;
 }
 void build_tree_set_shape(Index& ix, u32 nvalid)
 {

@@ -364,6 +364,8 @@ int build_box_and_codes(Index& ix, const float* d_xyz_src, u64 n, const pcpx_bui
                         u32* d_hist12);
 int build_tree_from_sorted(Index& ix, u32 n_at_most, bool count_on_device);  // leaf records, boxes, levels from the sorted words / d_rec
 void build_tree_set_shape(Index& ix, u32 nvalid);
+// the shape of the tree over nvalid points, for pcpx_debug_tree: leaves, depth, and per level d <= depth the nodes the build writes
+void build_tree_shape(u32 nvalid, u32* nleaves, int* depth, u32 (&written)[MAXDEPTH + 1]);
 int sort_for_build(Index& ix, const u64* d_words, u64 n, const float* d_xyz_src, const float4* d_rec_in, u32* tile_hist_ready);
 constexpr u32 BUILD_REDO_WORD0 = 16;  // Index::d_scalars[16 .. 24): buckets whose runs the finish kernel could not order
 void free_shard(Index& ix);
@@ -409,7 +411,13 @@ struct SortPayload {
         const u32* bucket_first_pass = nullptr;  // 256 entries (device)
     }* finish_out = nullptr;
 };
-constexpr u32 SORT_RUN_TARGET = 16;     // (a run the finish kernel can order is at most 64 words: four times the average it plans for)
+constexpr u32 SORT_RUN_TARGET = 16;     // (the finish kernel orders runs of up to FIN_RUN_MAX words: four times the average it plans for)
+// k_finish (pcpx_build.hip) takes FIN_MARGIN words on either side of its tile into LDS and orders every run of at most FIN_RUN_MAX
+// words -- a run's word counts the FIN_RUN_MAX - 1 others in FIN_MARGIN steps, and such a run with a word in the tile lies inside
+// the window whole.  The bucket of a longer run takes every radix pass (Index::full_buckets).  This is the one place the number is
+// stated: tests/build_model.py reads it from here.
+constexpr int FIN_MARGIN = 64;
+constexpr int FIN_RUN_MAX = FIN_MARGIN + 1;
 int sort_keys_u64(void* tmp, size_t& tmp_bytes, const u64* kin, u64* kout, u64 n, hipStream_t s, int first_bit = 0,
                   const SortPayload* payload = nullptr);
 const u32* sort_failure_flag(void* tmp);

@@ -619,6 +619,10 @@ TmpLayout tmp_layout(u64 n)
 // payload (the index build): see SortPayload in pcpx_internal.h.
 int sort_keys_u64(void* tmp, size_t& tmp_bytes, const u64* kin, u64* kout, u64 n, hipStream_t s, int first_bit, const SortPayload* payload)
 {
+    if (first_bit < 0 || first_bit > 56 || (first_bit & 7)) {  // (whatever n is: an empty sort with a bit it cannot start from is refused too)
+        set_error("pcpx: radix sort first_bit %d", first_bit);
+        return PCPX_ERR_INVALID;
+    }
     const TmpLayout L = tmp_layout(n);
     if (!tmp) {
         tmp_bytes = L.total;
@@ -629,8 +633,8 @@ int sort_keys_u64(void* tmp, size_t& tmp_bytes, const u64* kin, u64* kout, u64 n
         return PCPX_ERR_INVALID;
     }
     if (n == 0) return PCPX_OK;
-    if (first_bit < 0 || first_bit > 56 || (first_bit & 7) || n >= (1ull << 32) - SORT_TILE) {
-        set_error("pcpx: radix sort first_bit %d / n %llu", first_bit, static_cast<unsigned long long>(n));
+    if (n >= (1ull << 32) - SORT_TILE) {
+        set_error("pcpx: radix sort of n = %llu words", static_cast<unsigned long long>(n));
         return PCPX_ERR_INVALID;
     }
     char* base = static_cast<char*>(tmp);

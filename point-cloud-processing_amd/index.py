@@ -953,6 +953,26 @@ class Index:
             check(self._lib.pcpx_debug_group_times(self._h, _vp(out), ng.value, C.byref(ng)))
         return out
 
+    def debug_tree(self):
+        """pcpx_debug_tree (for tests): the structure the last build left, as host arrays.  A dict of n (indexed points), nleaves, depth,
+        written (nodes the build writes per level 0 ... depth), leaves (nleaves x 32 uint32: x[8], y[8], z[8], id[8] as bits), nodes
+        (heap order x 8 uint32: lo[3], hi[3], poison, 0 as bits; defined are written[d] nodes from (4^d - 1) / 3 of every level) and
+        first_pass (256 uint32; zeros: the last build sorted nothing)."""
+        shape = (C.c_uint64 * 20)()
+        fp = np.zeros(256, np.uint32)
+        st = self._lib.pcpx_debug_tree(self._h, shape, None, 0, None, 0, fp.ctypes.data_as(_capi.u32p))
+        if st not in (_capi.PCPX_OK, _capi.PCPX_ERR_CAPACITY):
+            check(st)
+        nleaves, depth, nnodes = int(shape[1]), int(shape[2]), int(shape[3])
+        leaves = np.zeros((nleaves, 32), np.uint32)
+        nodes = np.zeros((nnodes, 8), np.uint32)
+        # (never a null array pointer, also for an empty tree: NULL asks for the sizes)
+        spare = np.zeros(8, np.uint32)
+        check(self._lib.pcpx_debug_tree(self._h, shape, _vp(leaves if nleaves else spare), nleaves, _vp(nodes if nnodes else spare), nnodes,
+                                        fp.ctypes.data_as(_capi.u32p)))
+        return {"n": int(shape[0]), "nleaves": nleaves, "depth": depth, "written": [int(shape[4 + d]) for d in range(depth + 1)] if nleaves else [],
+                "leaves": leaves, "nodes": nodes, "first_pass": fp}
+
     def knn_batch_dev(self, d_queries, nq, k, eps, d_idx, d_cnt, d_d2=None):
         """kNN of nq arbitrary device-resident query points (curve-sorted internally, rows in query order)."""
         check(self._lib.pcpx_knn_batch_dev(self._h, d_queries, nq, k, eps, d_idx, d_cnt, d_d2))

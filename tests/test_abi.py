@@ -104,7 +104,7 @@ def test_null_handle_is_refused_everywhere(lib):
     import importlib
     capi = importlib.import_module("point-cloud-processing_amd._capi")
     names = _handle_functions()
-    assert len(names) == 43, names
+    assert len(names) == 44, names
     for name in names:
         res, argtypes = capi.SIGNATURES[name]
         args = [None if (t is None or issubclass(t, (C._Pointer, C.c_void_p, C.c_char_p))) else t() for t in argtypes]

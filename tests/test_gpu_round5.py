@@ -278,8 +278,8 @@ def test_device_resident_range_lists_of_every_point(pkg, oracle, kind, n, radius
 
 @pytest.mark.parametrize("copies,k", [(300, 15), (70, 32), (5000, 8)])
 def test_build_with_runs_the_leaf_kernel_cannot_order(pkg, oracle, copies, k):
-    """The sort stops after two bucketed passes where runs are expected to stay short and k_finish orders runs of up to 64 words in
-    LDS (csrc/pcpx_build.hip).  Hundreds of coincident points in an otherwise sparse bucket are one long run of equal keys: the
+    """The sort stops after two bucketed passes where runs are expected to stay short and k_finish orders runs of up to FIN_RUN_MAX
+    words (65: csrc/pcpx_internal.h) in LDS (csrc/pcpx_build.hip).  Hundreds of coincident points in an otherwise sparse bucket are one long run of equal keys: the
     build must notice, repeat itself with that bucket taking every pass, and give the same rows as brute force -- also on the
     rebuild after it (the handle remembers the bucket) and through a rank-local handle."""
     torch = _torch()
@@ -295,8 +295,11 @@ def test_build_with_runs_the_leaf_kernel_cannot_order(pkg, oracle, copies, k):
     grid = np.array([0, 0, 0, 1, 1, 1], np.float32)
     d_pts = torch.from_numpy(pts).to(dev)
     ix = pkg.Index.from_device(d_pts.data_ptr(), n, voxel_grid=grid)
+    import build_model  # (the host model of the build says which buckets exactly: tests/test_gpu_build_order.py)
+    model = build_model.Model(pts, grid)
+    assert ix.debug_get("build_redos") == model.build_redos and ix.debug_get("full_buckets") == len(model.redo)
     if copies <= 300:  # knots of a few hundred points: the plan (words per cell of the bucket's fullest 16-bit cell) lets their buckets stop early ...
-        assert ix.debug_get("build_redos") == 1 and 1 <= ix.debug_get("full_buckets") <= 12  # ... and the first attempt finds them out
+        assert ix.debug_get("build_redos") == 1 and 1 <= len(model.redo) <= 12  # ... and the first attempt finds them out
     else:              # knots of thousands: the plan sends their buckets through every pass from the start
         assert ix.debug_get("build_redos") == 0
     sel = np.concatenate([rng.integers(0, n, 400), np.nonzero((pts[:, None, :] == hot[None, :3, :]).all(2).any(1))[0][:100]])
