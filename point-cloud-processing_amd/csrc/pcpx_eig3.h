@@ -1,11 +1,28 @@
-// pcpx_eig3.h -- PCA normal of a 3x3 scatter matrix on the device (shared by the fused kNN kernel and k_normals).
+// pcpx_eig3.h -- PCA normal of a 3x3 scatter matrix (shared by the fused kNN kernel, k_normals, the radius normals, MLS and the
+// shape features).  Device code under hipcc; alone, a plain C++ program can include it too (tests/cpp/eig3_shape.cpp), where one
+// "lane" is the whole wave.
 #ifndef PCPX_EIG3_H
 #define PCPX_EIG3_H
 
+#if defined(__HIPCC__)
 #include "pcpx_device.h"
+#define PCPX_EIG3_INLINE __device__ __forceinline__
+#define PCPX_EIG3_FN __device__
+#else
+#include <cmath>
+#include <limits>
+#define PCPX_EIG3_INLINE inline
+#define PCPX_EIG3_FN inline
+#endif
 
 namespace pcpx {
 namespace {
+
+#if defined(__HIPCC__)
+__device__ __forceinline__ bool eig_any(bool c) { return any_lane(c); }
+#else
+inline bool eig_any(bool c) { return c; }
+#endif
 
 // ------------------------------------------------------------------------------------------------
 // PCA normal of one neighbourhood per thread.
@@ -14,50 +31,138 @@ namespace {
 // ::compute (scale, closed-form 3x3 tridiagonalisation, implicit-shift QL, ascending sort), column of
 // the smallest eigenvalue with the reference's "last tie wins" ifs.  All in float32 without FMA, in
 // the same operation order as the CPU restatement used by the tests, so results are bit-comparable with it.
+//
+// The QL part is shaped for a wave: the 64 lanes of a wave sit in different branches of Eigen's code in the same trip (which
+// Givens arm, which column pair, which end), and a wave pays for every branch one of its lanes takes.  So each lane evaluates
+// one arm on selected operands and discards what it does not need; the float operations a lane keeps, and their order, are
+// Eigen's (tests/cpp/eig3_shape.cpp compares with the branching form bit for bit).
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void make_givens(float p, float q, float& c, float& s)
+
+// Eigen's two arms, |p| > |q| and not, are one: t = num / den, u = +-sqrt(1 + t^2), r = 1 / u, m = t r, and
+//   |p| > |q|:  c = 1 / u = r,                   s = -t c = -(t r) = -m
+//   otherwise:  s = -1 / u = -(1 / u) = -r,      c = -t s = (-t)(-r) = t r = m
+// (negation commutes with a rounded product or quotient).  A lane with p == 0 or q == 0 divides 0 or by 0 and drops the result.
+PCPX_EIG3_INLINE void make_givens(float p, float q, float& c, float& s)
 {
-    if (q == 0.f) {
-        c = p < 0.f ? -1.f : 1.f;
-        s = 0.f;
-    } else if (p == 0.f) {
+    const bool big = fabsf(p) > fabsf(q);
+    const float num = big ? q : p, den = big ? p : q;
+    const float t = num / den;
+    float u = sqrtf(1.f + t * t);
+    if (den < 0.f) u = -u;
+    const float r = 1.f / u, m = t * r;
+    c = big ? r : m;
+    s = big ? -m : -r;
+    if (p == 0.f) {
         c = 0.f;
         s = q < 0.f ? 1.f : -1.f;
-    } else if (fabsf(p) > fabsf(q)) {
-        float t = q / p;
-        float u = sqrtf(1.f + t * t);
-        if (p < 0.f) u = -u;
-        c = 1.f / u;
-        s = -t * c;
-    } else {
-        float t = p / q;
-        float u = sqrtf(1.f + t * t);
-        if (q < 0.f) u = -u;
-        s = -1.f / u;
-        c = -t * s;
+    }
+    if (q == 0.f) {  // (tested first by Eigen: applied last)
+        c = p < 0.f ? -1.f : 1.f;
+        s = 0.f;
     }
 }
 
-__device__ __forceinline__ float eig_hypot(float x, float y)
+PCPX_EIG3_INLINE float eig_hypot(float x, float y)
 {
-    float ax = fabsf(x), ay = fabsf(y);
-    float p, qp;
-    if (ax > ay) {
-        p = ax;
-        qp = ay / p;
-    } else {
-        p = ay;
-        qp = ax / p;
+    const float ax = fabsf(x), ay = fabsf(y);
+    const bool xbig = ax > ay;
+    const float p = xbig ? ax : ay, qp = (xbig ? ay : ax) / p;
+    const float h = p * sqrtf(1.f + qp * qp);
+    return p == 0.f ? 0.f : h;
+}
+
+// The tridiagonal matrix {diagonal d, subdiagonal e} and the accumulated rotations Q, in registers.
+struct Ql3 {
+    float d0, d1, d2, e0, e1;
+    float q00, q10, q20, q01, q11, q21, q02, q12, q22;
+};
+
+constexpr int QL3_MAX_TRIPS = 90;  // Eigen's m_maxIterations * n = 30 * 3
+
+// Implicit-shift QL sweeps until both subdiagonal entries are deflated; false if a lane would need more than QL3_MAX_TRIPS trips
+// (it then stops where it is, as Eigen's NoConvergence does).  trips_done > 0 is for the test of that cap.
+// A trip works on the block start ... end of the lane: {0,1}, {0,2} or {1,2}.  Its one or two rotations sit at two fixed
+// sites, k = 0 on columns 0 and 1 for start == 0, then k = 1 on columns 1 and 2 for end == 2, each an exec-masked region that
+// is skipped when no lane wants it.  A lane that is done (end == 0) passes through selects that keep what it has.
+PCPX_EIG3_INLINE bool ql3_iterate(Ql3& m, int trips_done = 0)
+{
+    const float tiny = std::numeric_limits<float>::min();
+    const float precision = 2.f * std::numeric_limits<float>::epsilon();
+    float d0 = m.d0, d1 = m.d1, d2 = m.d2, e0 = m.e0, e1 = m.e1;
+    float q00 = m.q00, q10 = m.q10, q20 = m.q20, q01 = m.q01, q11 = m.q11, q21 = m.q21, q02 = m.q02, q12 = m.q12, q22 = m.q22;
+    int end = 2, start = 0;
+    bool converged = true;
+    for (int trip = trips_done + 1;; ++trip) {  // (a lane is in every trip until it is done: the count is the wave's)
+        if (start == 0 && end > 0 && (fabsf(e0) <= (fabsf(d0) + fabsf(d1)) * precision || fabsf(e0) <= tiny)) e0 = 0.f;
+        if (end == 2 && (fabsf(e1) <= (fabsf(d1) + fabsf(d2)) * precision || fabsf(e1) <= tiny)) e1 = 0.f;
+        if (end == 2 && e1 == 0.f) end = 1;
+        if (end == 1 && e0 == 0.f) end = 0;
+        if (end > 0 && trip > QL3_MAX_TRIPS) {
+            converged = false;
+            end = 0;
+        }
+        if (!eig_any(end > 0)) break;
+        start = (end == 2 && e0 != 0.f) ? 0 : end - 1;  // (-1 for a lane that is done: neither site, no deflation test)
+        // Wilkinson shift from the trailing 2x2 block
+        const bool two = end == 2;
+        const float dem1 = two ? d1 : d0, de = two ? d2 : d1, ee = two ? e1 : e0;
+        const float td = (dem1 - de) * 0.5f;
+        const float e2 = ee * ee;
+        const float h = eig_hypot(td, ee);
+        float mu = de - e2 / (td + (td > 0.f ? h : -h));
+        const bool e2_underflowed = end > 0 && td != 0.f && e2 == 0.f;
+        if (eig_any(e2_underflowed)) {
+            const float other = de - (ee / (td + (td > 0.f ? 1.f : -1.f))) * (ee / h);
+            mu = e2_underflowed ? other : mu;
+        }
+        if (td == 0.f) mu = de - fabsf(ee);
+        float x = (start == 0 ? d0 : d1) - mu;
+        float z = start == 0 ? e0 : e1;
+        if (start == 0) {  // k = 0: rows and columns 0, 1
+            float c, s;
+            make_givens(x, z, c, s);
+            const float sdk = s * d0 + c * e0;
+            const float dkp1 = s * e0 + c * d1;
+            const float ndk = c * (c * d0 - s * e0) - s * (c * e0 - s * d1);
+            d0 = ndk;
+            d1 = s * sdk + c * dkp1;
+            e0 = c * sdk - s * dkp1;
+            x = e0;
+            if (end == 2) {  // the bulge for k = 1
+                z = -s * e1;
+                e1 = c * e1;
+            }
+            float a, b;
+            a = q00; b = q01; q00 = c * a - s * b; q01 = s * a + c * b;
+            a = q10; b = q11; q10 = c * a - s * b; q11 = s * a + c * b;
+            a = q20; b = q21; q20 = c * a - s * b; q21 = s * a + c * b;
+        }
+        if (end == 2) {  // k = 1: rows and columns 1, 2
+            float c, s;
+            make_givens(x, z, c, s);
+            const float sdk = s * d1 + c * e1;
+            const float dkp1 = s * e1 + c * d2;
+            const float ndk = c * (c * d1 - s * e1) - s * (c * e1 - s * d2);
+            d1 = ndk;
+            d2 = s * sdk + c * dkp1;
+            e1 = c * sdk - s * dkp1;
+            if (start == 0) e0 = c * e0 - s * z;
+            float a, b;
+            a = q01; b = q02; q01 = c * a - s * b; q02 = s * a + c * b;
+            a = q11; b = q12; q11 = c * a - s * b; q12 = s * a + c * b;
+            a = q21; b = q22; q21 = c * a - s * b; q22 = s * a + c * b;
+        }
     }
-    if (p == 0.f) return 0.f;
-    return p * sqrtf(1.f + qp * qp);
+    m.d0 = d0; m.d1 = d1; m.d2 = d2; m.e0 = e0; m.e1 = e1;
+    m.q00 = q00; m.q10 = q10; m.q20 = q20; m.q01 = q01; m.q11 = q11; m.q21 = q21; m.q02 = q02; m.q12 = q12; m.q22 = q22;
+    return converged;
 }
 
 // AXIS: also the column of the largest eigenvalue after the ascending sort (column 2) in axis[3] -- the principal axis of the
 // shape features (pcpx_range.hip, k_range_features); the default form is what every other caller compiles.
 template <bool AXIS = false>
-__device__ void eig3_smallest(float a00, float a10, float a20, float a11, float a21, float a22, float normal[3],
-                              float evals[3], float* axis = nullptr)
+PCPX_EIG3_FN void eig3_smallest(float a00, float a10, float a20, float a11, float a21, float a22, float normal[3],
+                                float evals[3], float* axis = nullptr)
 {
     float scale = fmaxf(fmaxf(fmaxf(fabsf(a00), fabsf(a10)), fmaxf(fabsf(a20), fabsf(a11))),
                         fmaxf(fabsf(a21), fabsf(a22)));
@@ -82,67 +187,10 @@ __device__ void eig3_smallest(float a00, float a10, float a20, float a11, float 
         q11 = m01; q21 = m02; q12 = m02; q22 = -m01;
     }
     // registers instead of arrays: diag = {d0,d1,d2}, sub = {e0,e1}, Q columns {q?0,q?1,q?2}
-    const float precision = 2.f * std::numeric_limits<float>::epsilon();
-    int end = 2, start = 0, iter = 0;
-    bool converged = true;
-    auto rot_cols01 = [&](float c, float s) {
-        float x, y;
-        x = q00; y = q01; q00 = c * x - s * y; q01 = s * x + c * y;
-        x = q10; y = q11; q10 = c * x - s * y; q11 = s * x + c * y;
-        x = q20; y = q21; q20 = c * x - s * y; q21 = s * x + c * y;
-    };
-    auto rot_cols12 = [&](float c, float s) {
-        float x, y;
-        x = q01; y = q02; q01 = c * x - s * y; q02 = s * x + c * y;
-        x = q11; y = q12; q11 = c * x - s * y; q12 = s * x + c * y;
-        x = q21; y = q22; q21 = c * x - s * y; q22 = s * x + c * y;
-    };
-    while (end > 0) {
-        if (start <= 0 && 0 < end)
-            if (fabsf(e0) <= (fabsf(d0) + fabsf(d1)) * precision || fabsf(e0) <= tiny) e0 = 0.f;
-        if (start <= 1 && 1 < end)
-            if (fabsf(e1) <= (fabsf(d1) + fabsf(d2)) * precision || fabsf(e1) <= tiny) e1 = 0.f;
-        while (end > 0 && (end == 2 ? e1 : e0) == 0.f) end--;
-        if (end <= 0) break;
-        iter++;
-        if (iter > 90) { converged = false; break; }
-        start = end - 1;
-        while (start > 0 && (start == 1 ? e0 : 0.f) != 0.f) start--;
-        // tridiagonal_qr_step(start, end)
-        float dem1 = end == 2 ? d1 : d0, de = end == 2 ? d2 : d1, ee = end == 2 ? e1 : e0;
-        float td = (dem1 - de) * 0.5f;
-        float mu = de;
-        if (td == 0.f) {
-            mu -= fabsf(ee);
-        } else {
-            float e2 = ee * ee;
-            float h = eig_hypot(td, ee);
-            if (e2 == 0.f) mu -= (ee / (td + (td > 0.f ? 1.f : -1.f))) * (ee / h);
-            else mu -= e2 / (td + (td > 0.f ? h : -h));
-        }
-        float x = (start == 0 ? d0 : d1) - mu;
-        float z = start == 0 ? e0 : e1;
-        for (int k = start; k < end; ++k) {
-            float c, s;
-            make_givens(x, z, c, s);
-            float dk = k == 0 ? d0 : d1, dk1 = k == 0 ? d1 : d2, sk = k == 0 ? e0 : e1;
-            float sdk = s * dk + c * sk;
-            float dkp1 = s * sk + c * dk1;
-            float ndk = c * (c * dk - s * sk) - s * (c * sk - s * dk1);
-            float ndk1 = s * sdk + c * dkp1;
-            float nsk = c * sdk - s * dkp1;
-            if (k == 0) { d0 = ndk; d1 = ndk1; e0 = nsk; }
-            else { d1 = ndk; d2 = ndk1; e1 = nsk; }
-            if (k > start) e0 = c * e0 - s * z;  // k == 1, start == 0: sub[k-1] = sub[0]
-            x = nsk;
-            if (k < end - 1) {  // k == 0, end == 2
-                z = -s * e1;
-                e1 = c * e1;
-            }
-            if (k == 0) rot_cols01(c, s);
-            else rot_cols12(c, s);
-        }
-    }
+    Ql3 m = {d0, d1, d2, e0, e1, q00, q10, q20, q01, q11, q21, q02, q12, q22};
+    const bool converged = ql3_iterate(m);
+    d0 = m.d0; d1 = m.d1; d2 = m.d2;
+    q00 = m.q00; q10 = m.q10; q20 = m.q20; q01 = m.q01; q11 = m.q11; q21 = m.q21; q02 = m.q02; q12 = m.q12; q22 = m.q22;
     if (converged) {
         // ascending selection sort (first minimum wins), swapping eigenvector columns
         auto swap01 = [&]() {
@@ -181,4 +229,6 @@ __device__ void eig3_smallest(float a00, float a10, float a20, float a11, float 
 }  // namespace
 }  // namespace pcpx
 
+#undef PCPX_EIG3_INLINE
+#undef PCPX_EIG3_FN
 #endif

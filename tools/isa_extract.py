@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Extracts one kernel's ISA from `hipcc -S --cuda-device-only` output and prints instruction-class counts
 per basic block (VALU / SALU / SMEM / LDS / VMEM / scratch), to see where a hot loop spends its issue slots.
+The counts are static: a loop's body counts once however many trips it takes (the assembly marks blocks "in Loop: Header=..."),
+so a budget made from them needs the trip counts as well (the epilogue row).
 usage: tools/isa_extract.py file.s <substring of the mangled kernel name> [out.s]"""
 import re
 import sys
