@@ -334,6 +334,15 @@ ICP_SIGNATURES = {
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/pcpx_gicp.h (Generalized ICP: the loop with a plane-to-plane step)
+PCPX_GICP_COVARIANCES = 1
+PCPX_GICP_ON_DEVICE = 2
+_GICP_ARGS = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
+              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+GICP_SIGNATURES = {
+    "pcpx_gicp_rigid": (C.c_int, list(_GICP_ARGS)),
+}
+
 # name -> (restype, argtypes); every symbol declared in include/pcpx_planes.h (plane detection)
 PCPX_PLANE_REFIT = 1
 PCPX_PLANE_NORMALS = 2
@@ -453,7 +462,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(RADIUS_SIGNATURES.items()) + list(CLUSTER_SIGNATURES.items())\
             + list(SUBSAMPLE_SIGNATURES.items()) + list(SEGMENT_SIGNATURES.items()) + list(FEATURES_SIGNATURES.items())\
             + list(KEYPOINTS_SIGNATURES.items()) + list(DESCRIPTORS_SIGNATURES.items()) + list(MATCH_SIGNATURES.items())\
-            + list(REGISTER_SIGNATURES.items()) + list(ICP_SIGNATURES.items()) + list(PLANES_SIGNATURES.items())\
+            + list(REGISTER_SIGNATURES.items()) + list(ICP_SIGNATURES.items()) + list(GICP_SIGNATURES.items()) + list(PLANES_SIGNATURES.items())\
             + list(VOXEL_SIGNATURES.items()) + list(MLS_SIGNATURES.items()) + list(OUTLIERS_SIGNATURES.items())\
             + list(BOUNDARY_SIGNATURES.items()) + list(OBJECTS_SIGNATURES.items()) + list(FPS_SIGNATURES.items())\
             + list(SHAPES_SIGNATURES.items()):

@@ -12,14 +12,14 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 OBJ_DIR = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libpcpx.so")
-SOURCES = ["pcpx_query.hip", "pcpx_few.hip", "pcpx_range.hip", "pcpx_cluster.hip", "pcpx_segment.hip", "pcpx_subsample.hip", "pcpx_keypoints.hip", "pcpx_outliers.hip", "pcpx_boundary.hip", "pcpx_fps.hip", "pcpx_descriptors.hip", "pcpx_match.hip", "pcpx_register.hip", "pcpx_icp.hip", "pcpx_planes.hip", "pcpx_shapes.hip", "pcpx_voxel.hip", "pcpx_objects.hip", "pcpx_mls.hip", "pcpx_filter.hip", "pcpx_normals.hip", "pcpx_prep.hip", "pcpx_orient.hip", "pcpx_build.hip", "pcpx_shard.hip", "pcpx_sort.hip",
+SOURCES = ["pcpx_query.hip", "pcpx_few.hip", "pcpx_range.hip", "pcpx_cluster.hip", "pcpx_segment.hip", "pcpx_subsample.hip", "pcpx_keypoints.hip", "pcpx_outliers.hip", "pcpx_boundary.hip", "pcpx_fps.hip", "pcpx_descriptors.hip", "pcpx_match.hip", "pcpx_register.hip", "pcpx_icp.hip", "pcpx_gicp.hip", "pcpx_planes.hip", "pcpx_shapes.hip", "pcpx_voxel.hip", "pcpx_objects.hip", "pcpx_mls.hip", "pcpx_filter.hip", "pcpx_normals.hip", "pcpx_prep.hip", "pcpx_orient.hip", "pcpx_build.hip", "pcpx_shard.hip", "pcpx_sort.hip",
            "pcpx_comm.hip", "pcpx_kd.hip", "pcpx_isosurface.hip", "pcpx_simplify.hip", "pcpx_runtime.hip", "pcpx_api.hip"]
 HEADERS = [os.path.join(CSRC, "pcpx_internal.h"), os.path.join(CSRC, "pcpx_device.h"), os.path.join(CSRC, "pcpx_box_bound.h"), os.path.join(CSRC, "pcpx_path_start.h"), os.path.join(CSRC, "pcpx_eig3.h"), os.path.join(CSRC, "pcpx_curve.h"),
            os.path.join(CSRC, "pcpx_curve_table.h"), os.path.join(CSRC, "pcpx_scan.h"), os.path.join(CSRC, "pcpx_unionfind.h"), os.path.join(CSRC, "pcpx_labels.h"), os.path.join(CSRC, "pcpx_keep.h"), os.path.join(CSRC, "pcpx_stage.h"), os.path.join(CSRC, "pcpx_lease.h"), os.path.join(CSRC, "pcpx_horn.h"), os.path.join(CSRC, "pcpx_plane_solve.h"), os.path.join(CSRC, "pcpx_ransac.h"), os.path.join(CSRC, "pcpx_fixed_sum.h"), os.path.join(CSRC, "pcpx_plane_fit.h"),
            os.path.join(INCLUDE, "pcpx.h"), os.path.join(INCLUDE, "pcpx_radius.h"), os.path.join(INCLUDE, "pcpx_cluster.h"),
            os.path.join(INCLUDE, "pcpx_subsample.h"), os.path.join(INCLUDE, "pcpx_segment.h"), os.path.join(INCLUDE, "pcpx_features.h"),
            os.path.join(INCLUDE, "pcpx_keypoints.h"), os.path.join(INCLUDE, "pcpx_descriptors.h"), os.path.join(INCLUDE, "pcpx_match.h"),
-           os.path.join(INCLUDE, "pcpx_register.h"), os.path.join(INCLUDE, "pcpx_icp.h"), os.path.join(INCLUDE, "pcpx_planes.h"), os.path.join(INCLUDE, "pcpx_voxel.h"), os.path.join(INCLUDE, "pcpx_mls.h"), os.path.join(INCLUDE, "pcpx_outliers.h"), os.path.join(INCLUDE, "pcpx_boundary.h"), os.path.join(INCLUDE, "pcpx_fps.h"), os.path.join(INCLUDE, "pcpx_objects.h"), os.path.join(INCLUDE, "pcpx_shapes.h")]
+           os.path.join(INCLUDE, "pcpx_register.h"), os.path.join(INCLUDE, "pcpx_icp.h"), os.path.join(INCLUDE, "pcpx_gicp.h"), os.path.join(INCLUDE, "pcpx_planes.h"), os.path.join(INCLUDE, "pcpx_voxel.h"), os.path.join(INCLUDE, "pcpx_mls.h"), os.path.join(INCLUDE, "pcpx_outliers.h"), os.path.join(INCLUDE, "pcpx_boundary.h"), os.path.join(INCLUDE, "pcpx_fps.h"), os.path.join(INCLUDE, "pcpx_objects.h"), os.path.join(INCLUDE, "pcpx_shapes.h")]
 ARCH = "gfx950"
 # -ffp-contract=off: the reference evaluates dx*dx+dy*dy+dz*dz without FMA; neighbour order and the
 # eigen-solver restatement are only bit-comparable with it if the GPU does not fuse either.

@@ -8,6 +8,7 @@
 //   k_fixed_partial / k_fixed_final (pcpx_fixed_sum.h) over PlaneSystem, k_plane_solve   the point-to-plane step: 29 float64 sums in
 //                     the fits' fixed order, Cholesky
 // The point-to-point step is the rigid fit of pcpx_register.hip through fit_pairs_device: the same kernels, so the same bits.
+// icp_loop_device runs the same loop around a caller's sums in the point-to-plane layout (pcpx_gicp.hip: the plane-to-plane step).
 #include "pcpx_device.h"
 #include "pcpx_fixed_sum.h"
 #include "pcpx_icp.h"
@@ -335,12 +336,27 @@ int check_nearest(const char* what, const void* s, u64 m, float radius)
     return PCPX_OK;
 }
 
-int check_loop(const char* what, u32 max_iterations, u32 flags, const void* normals, const void* transform)
+int check_iterations(const char* what, u32 max_iterations)
 {
     if (max_iterations < 1u || max_iterations > PCPX_ICP_MAX_ITERATIONS) {
         set_error("%s: max_iterations = %u is not in 1 .. %u", what, max_iterations, PCPX_ICP_MAX_ITERATIONS);
         return PCPX_ERR_INVALID;
     }
+    return PCPX_OK;
+}
+
+int check_transform(const char* what, const void* transform)
+{
+    if (!transform) {
+        set_error("%s: the transform array is NULL", what);
+        return PCPX_ERR_INVALID;
+    }
+    return PCPX_OK;
+}
+
+int check_loop(const char* what, u32 max_iterations, u32 flags, const void* normals, const void* transform)
+{
+    if (const int st = check_iterations(what, max_iterations)) return st;
     if (flags & ~PCPX_ICP_POINT_TO_PLANE) {
         set_error("%s: unknown flag bits 0x%x", what, flags & ~PCPX_ICP_POINT_TO_PLANE);
         return PCPX_ERR_INVALID;
@@ -353,11 +369,7 @@ int check_loop(const char* what, u32 max_iterations, u32 flags, const void* norm
         set_error("%s: normals without PCPX_ICP_POINT_TO_PLANE", what);
         return PCPX_ERR_INVALID;
     }
-    if (!transform) {
-        set_error("%s: the transform array is NULL", what);
-        return PCPX_ERR_INVALID;
-    }
-    return PCPX_OK;
+    return check_transform(what, transform);
 }
 
 // the source order: the curve sort of the moved points by the machinery of pcpx_prep.hip, copied out of the handle's scratch (which
@@ -426,19 +438,15 @@ int nearest_device(Index& ix, const float* d_s, u64 m64, const double* d_pose, f
     });
 }
 
-struct LoopOut {
-    double* transform;
-    u32 *status, *iterations, *last_count, *count_trace;
-    double* rms_trace;
-    u32* partner;
-};
+using LoopOut = IcpLoopOut;
 
+// custom: the round's sums by the caller's step (icp_loop_device) instead of one of the two modes of `flags`
 int icp_device(Index& ix, const float* d_s, u64 m64, const double* d_pose, float radius, u32 max_iterations, u32 flags, const float* d_normals,
-               const LoopOut& out)
+               const LoopOut& out, const char* what = "pcpx_icp_rigid", const IcpSumsStep* custom = nullptr)
 {
     const bool plane = (flags & PCPX_ICP_POINT_TO_PLANE) != 0u;
     if (ix.n_in && !ix.d_xyz) {
-        set_error("pcpx_icp_rigid: the handle keeps no copy of its cloud");
+        set_error("%s: the handle keeps no copy of its cloud", what);
         return PCPX_ERR_UNSUPPORTED;
     }
     const u32 m = static_cast<u32>(m64);
@@ -466,8 +474,13 @@ int icp_device(Index& ix, const float* d_s, u64 m64, const double* d_pose, float
                 k_nearest_posed<<<grid_for_groups(groups), 64 * WAVES_PER_BLOCK, 0, s>>>(t, groups, m, d_s, order, state->pose, radius, &state->done, nullptr,
                                                                                        nullptr, pairs[k & 1u], k > 0 ? pairs[(k - 1u) & 1u] : nullptr,
                                                                                        k > 0 && previous_start ? ix.d_xyz : nullptr, state->slots);
-            k_icp_decide<<<1, 64, 0, s>>>(state, k, plane ? 6u : 3u, m);
-            if (plane) {
+            k_icp_decide<<<1, 64, 0, s>>>(state, k, custom ? custom->min_count : plane ? 6u : 3u, m);
+            if (custom) {
+                if ((st = custom->enqueue(custom->ctx, state->pose, &state->done, state->plane, reinterpret_cast<const u32*>(pairs[k & 1u]), plane_partial,
+                                          s)) != PCPX_OK)
+                    return st;
+                k_plane_solve<<<1, 64, 0, s>>>(state, o[0], o[1], o[2]);
+            } else if (plane) {
                 const PlaneIn in{d_s, ix.d_xyz, d_normals, pairs[k & 1u], m, static_cast<u32>(ix.n_in), {o[0], o[1], o[2]}};
                 fixed_sum(PlaneSystem{in, state, {}}, plane_partial, s);
                 k_plane_solve<<<1, 64, 0, s>>>(state, o[0], o[1], o[2]);
@@ -498,6 +511,19 @@ int booked_as_one_range_interval(Index& ix, Body&& body)
 }
 
 }  // namespace
+
+int icp_check_arguments(const char* what, const void* s, u64 m, float radius, u32 max_iterations, const void* transform)
+{
+    int st = check_nearest(what, s, m, radius);
+    if (st != PCPX_OK || (st = check_iterations(what, max_iterations)) != PCPX_OK) return st;
+    return check_transform(what, transform);
+}
+
+int icp_loop_device(Index& ix, const char* what, const float* d_s, u64 m, const double* d_pose, float radius, u32 max_iterations,
+                    const IcpSumsStep& step, const IcpLoopOut& out)
+{
+    return booked_as_one_range_interval(ix, [&] { return icp_device(ix, d_s, m, d_pose, radius, max_iterations, 0u, nullptr, out, what, &step); });
+}
 
 }  // namespace pcpx
 

@@ -512,6 +512,26 @@ int launch_invert_perm(const u32* d_perm, u64 n, u32* d_position_of, hipStream_t
 size_t fit_scratch_bytes();
 int fit_pairs_device(const float* d_p, u32 np, const float* d_q, u32 nq, const u32* d_pairs, u32 capacity, const u64* d_count, void* d_scratch,
                      const double* d_fallback, double* d_out, double* d_out_rms, hipStream_t s);
+// icp.hip: the loop of pcpx_icp_rigid_dev (search, the loop's rules, the lease, one PCPX_K_RANGE interval) around a step of the
+// caller's: `enqueue` puts on s what leaves this round's 29 sums of the point-to-plane layout (21 of A, 6 of b, the sum of squares,
+// the rows) in d_sums; the loop follows it with its own Cholesky solve and commit.  It gets device addresses only: the round's pose
+// (12 doubles are read), the word that is not 0 once the loop has stopped (the sums then count no rows), the round's pairs ({source
+// row, partner} by source row, m of them) and FIT_BLOCKS x 32 doubles for partial sums.  min_count: "too few partners" of step 4.
+struct IcpSumsStep {
+    int (*enqueue)(void* ctx, const double* d_pose, const u32* d_done, double* d_sums, const u32* d_pairs, double* d_partial, hipStream_t s);
+    void* ctx;
+    u32 min_count;
+};
+struct IcpLoopOut {
+    double* transform;
+    u32 *status, *iterations, *last_count, *count_trace;
+    double* rms_trace;
+    u32* partner;
+};
+int icp_loop_device(Index& ix, const char* what, const float* d_s, u64 m, const double* d_pose, float radius, u32 max_iterations,
+                    const IcpSumsStep& step, const IcpLoopOut& out);
+// ... and its argument checks (the radius, m, the source array; max_iterations, the transform array), with `what` in the text
+int icp_check_arguments(const char* what, const void* s, u64 m, float radius, u32 max_iterations, const void* transform);
 
 // ---- the runtime (pcpx_runtime.hip) ---------------------------------------------------------------------------------------------
 extern thread_local std::string g_err;  // the thread's error text (pcpx_last_error)

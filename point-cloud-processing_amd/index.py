@@ -783,6 +783,56 @@ class Index:
                                            *(self._dptr(d) for d in (d_normals, d_transform, d_status, d_iterations, d_last_count, d_count, d_rms,
                                                                      d_partner))))
 
+    # ---- Generalized ICP (include/pcpx_gicp.h) ----
+    def gicp(self, source, radius, source_normals=None, normals=None, epsilon=1e-3, pose=None, max_iterations=50, source_cov=None, cov=None,
+             want_partner=False):
+        """Generalized ICP of `source` onto this cloud from `pose` (None: the identity): the loop of icp() with a plane-to-plane
+        step -- a pair's residual is weighted by the inverse of C_target + R C_source R^T.  Either both clouds' normals
+        (`source_normals` (m, 3) by source row, `normals` (n_in, 3) by input row of this cloud; neither oriented nor unit length
+        needed) with `epsilon` in (0, 1], the variance along a normal relative to the variance across it; or both clouds'
+        covariances (`source_cov` (m, 6), `cov` (n_in, 6): the upper triangles xx, xy, xz, yy, yz, zz), with which epsilon is not
+        used.  Returns icp()'s dict; "rms" is the root mean Mahalanobis residual over the usable rows."""
+        s = _f32(source, 3)
+        by_cov = source_cov is not None or cov is not None
+        if by_cov and (source_normals is not None or normals is not None):
+            raise ValueError("normals or covariances, not both")
+        a, b, width = (source_cov, cov, 6) if by_cov else (source_normals, normals, 3)
+        if a is None or b is None:
+            raise ValueError("both clouds' normals, or both clouds' covariances")
+        a, b = _f32(a).reshape(-1), _f32(b).reshape(-1)
+        if len(a) != width * len(s) or len(b) != width * self.n_in:
+            raise ValueError("one row of %d per source point and per input point" % width)
+        if not len(b):
+            b = np.zeros(width, np.float32)  # (an empty target still passes an address: nothing is read through it)
+        it = int(max_iterations)
+        xf = np.empty(16, np.float64)
+        words = [C.c_uint32(0) for _ in range(3)]
+        count, rms = np.empty(max(it, 1), np.uint32), np.empty(max(it, 1), np.float64)
+        partner = np.empty(len(s), np.uint32) if want_partner else None
+        check(self._lib.pcpx_gicp_rigid(self._h, _vp(s) if len(s) else None, len(s), _vp(self._pose16(pose)), float(radius), it,
+                                        _capi.PCPX_GICP_COVARIANCES if by_cov else 0, _vp(a) if len(s) else None, _vp(b),
+                                        0.0 if by_cov else float(epsilon), _vp(xf), *(C.byref(w) for w in words), _vp(count), _vp(rms), _vp(partner)))
+        done = words[1].value
+        out = {"transform": xf.reshape(4, 4), "status": words[0].value, "iterations": done, "last_count": words[2].value,
+               "count": count[:done].copy(), "rms": rms[:done].copy()}
+        if want_partner:
+            out["partner"] = partner
+        return out
+
+    def gicp_dev(self, d_source, m, radius, d_transform, d_source_normals=None, d_normals=None, epsilon=1e-3, d_pose=None, max_iterations=50,
+                 d_source_cov=None, d_cov=None, d_status=None, d_iterations=None, d_last_count=None, d_count=None, d_rms=None, d_partner=None):
+        """Device form (pcpx_gicp_rigid with PCPX_GICP_ON_DEVICE): the arrays of icp_dev, and float32 normals ((m, 3) and (n_in, 3) -- what range_neighbourhoods_self_dev left on
+        the device goes straight in) or covariances ((m, 6) and (n_in, 6)).  All max_iterations rounds are enqueued on the index's
+        stream with no synchronisation and no read-back."""
+        by_cov = d_source_cov is not None or d_cov is not None
+        if by_cov and (d_source_normals is not None or d_normals is not None):
+            raise ValueError("normals or covariances, not both")
+        a, b = (d_source_cov, d_cov) if by_cov else (d_source_normals, d_normals)
+        check(self._lib.pcpx_gicp_rigid(self._h, self._dptr(d_source), int(m), self._dptr(d_pose), float(radius), int(max_iterations),
+                                        _capi.PCPX_GICP_ON_DEVICE | (_capi.PCPX_GICP_COVARIANCES if by_cov else 0), self._dptr(a), self._dptr(b),
+                                        0.0 if by_cov else float(epsilon),
+                                        *(self._dptr(d) for d in (d_transform, d_status, d_iterations, d_last_count, d_count, d_rms, d_partner))))
+
     # ---- normals ----
     def normals_knn_self(self, k, eps=1e-5, want_knn=False):
         nrm = np.empty((self.n_in, 3), np.float32)
